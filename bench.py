@@ -10,7 +10,21 @@ recovery, canonical ordering + duplicate rejection).  Per-GPU work is fixed,
 so scaling is weak; ranks take disjoint nonce ranges (nonce-space data
 parallelism) and the solution counts are summed with an RCCL all-reduce.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it builds the solvers, warms up,
+times K steps, writes the last step's outputs when --dump-outputs is given, checks the
+solutions-per-nonce floor and prints one JSON line. `--full` adds the checks that take work
+of their own after the timed region (the GPU/CPU re-verification below).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller, as float32
+`DIR/<name>.npy` (rank r > 0 appends `_rank<r>` to the name):
+* `solutions_per_nonce` [batch]: how many solutions each nonce of the batch yielded;
+* `solution_nonce` [S]: the batch slot of each of the step's S solutions, ascending;
+* `solutions` [S, 1344]: the bytes of each minimal-encoded solution, a nonce's solutions in
+  lexicographic order (the solver returns them in an order that depends on kernel timing).
+The headers and nonces depend only on the arguments, so two builds run with the same
+arguments solve the same inputs and their dumps compare entry for entry.
 
 `--gpus N` always drives N GPUs, one process per GPU over RCCL:
 * launched by torchrun (WORLD_SIZE set): WORLD_SIZE must equal N;
@@ -19,7 +33,7 @@ Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
   `python -m torch.distributed.run --nproc-per-node N ...` as a child, exiting
   with its status (the parent never touches the GPU).
 
-After timing, every solution of every timed step is re-checked by the GPU batch
+With --full, after timing, every solution of every timed step is re-checked by the GPU batch
 verifier; a solution it rejects is re-checked by the CPU verifier, and one that both reject fails
 the run (a GPU-only rejection is counted and reported). The mean solutions per nonce must be
 >= 1.85 (Equihash(200,9) yields ~1.88 per nonce; a lower figure means the solver
@@ -75,7 +89,11 @@ def parse(argv=None):
     # round-6 solver (88-112 all within 0.3% of it; profiles/equihash_r6.md); two solvers of 96
     # hold ~100 GiB of the GPU's 288 GB
     ap.add_argument("--batch", type=int, default=int(os.environ.get("BCP_EH_BATCH", "96")))
-    ap.add_argument("--verify", type=int, default=1, help="GPU-verify every solution after timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks that take work of their own: every solution of every timed "
+                         "step re-verified on the GPU, GPU rejections re-checked on the CPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--solvers", type=int, default=int(os.environ.get("BCP_EH_SOLVERS", "2")),
                     help="solvers in flight per GPU (each its own stream and buffers)")
     ap.add_argument("--pipeline", type=int, default=int(os.environ.get("BCP_EH_PIPELINE", "0")),
@@ -91,6 +109,8 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
     world = int(os.environ.get("WORLD_SIZE", "0"))
     rehearsal = os.environ.get("BCP_DIST_BACKEND", "nccl") != "nccl"
     if world == 0:
@@ -152,6 +172,50 @@ def dry_run(world):
         dist.destroy_process_group()
 
 
+# Template: CEquihashInput of a mainnet-shaped header (108 B), random-ish but fixed.
+HEADER = bytes((i * 37 + 11) & 0xFF for i in range(108))
+
+
+def step_states(native, batch, step, rank=0):
+    """The inputs of one step: the BLAKE2b state of HEADER + nonce for each nonce of the batch."""
+    sts = []
+    for b in range(batch):
+        # nonce lanes: rank in the top bytes, step/batch counters in the low bytes
+        nonce = struct.pack("<QQQQ", step * batch + b, 0, 0, rank)
+        st = native.EquihashState(200, 9)
+        st.update(HEADER + nonce)
+        sts.append(st)
+    return sts
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, per_nonce, rank=0):
+    """The last timed step's result as float32 arrays (layout in the module docstring). Past
+    DUMP_MAX_BYTES the dump keeps the leading nonces of the batch that fit."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    counts, slots, rows, size = [], [], [], 0
+    for b, sols in enumerate(per_nonce):
+        need = 4 * (1 + sum(1 + len(s) for s in sols))
+        if size + need > DUMP_MAX_BYTES:
+            break
+        size += need
+        counts.append(len(sols))
+        for s in sorted(sols):
+            slots.append(b)
+            rows.append(np.frombuffer(s, dtype=np.uint8))
+    sfx = f"_rank{rank}" if rank else ""
+    arrays = {
+        "solutions_per_nonce": np.asarray(counts, dtype=np.float32),
+        "solution_nonce": np.asarray(slots, dtype=np.float32),
+        "solutions": np.stack(rows).astype(np.float32) if rows else np.zeros((0, 0), dtype=np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{sfx}.npy"), a)
+
+
 def run(args, world):
     import torch
     import torch.distributed as dist
@@ -188,18 +252,9 @@ def run(args, world):
     torch.cuda.synchronize()
     # device memory the solvers took (ranks sharing a GPU in the rehearsal overlap here)
     solver_gib = (free0 - torch.cuda.mem_get_info(device)[0]) / 2**30
-    # Template: CEquihashInput of a mainnet-shaped header (108 B), random-ish but fixed.
-    header = bytes((i * 37 + 11) & 0xFF for i in range(108))
 
     def states_for(step):
-        sts = []
-        for b in range(args.batch):
-            # nonce lanes: rank in the top bytes, step/batch counters in the low bytes
-            nonce = struct.pack("<QQQQ", step * args.batch + b, 0, 0, rank)
-            st = native.EquihashState(200, 9)
-            st.update(header + nonce)
-            sts.append(st)
-        return sts
+        return step_states(native, args.batch, step, rank)
 
     for w in range(args.warmup):
         solvers[w % nsolv].solve(states_for(1_000_000 + w))
@@ -213,10 +268,13 @@ def run(args, world):
     nsol = 0
     pending = collections.deque()  # (step, solver) launched but not yet collected
 
+    last_step = None  # what the last timed step returned: per nonce, its solutions
+
     def collect():
-        nonlocal nsol
+        nonlocal nsol, last_step
         ps, psolver = pending.popleft()
-        for b, sols in enumerate(psolver.collect()):
+        last_step = psolver.collect()
+        for b, sols in enumerate(last_step):
             nsol += len(sols)
             sols_kept.extend((all_states[ps][b], x) for x in sols)
 
@@ -233,18 +291,21 @@ def run(args, world):
     barrier()
     dt = time.perf_counter() - t0
 
-    # verification happens after the timed region: every solution found in every step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step, rank)
+
+    # --full: verification happens after the timed region: every solution found in every step
     verified = None
     nbad = 0
     gpu_cpu_disagree = 0
-    if args.verify and sols_kept:
+    if args.full and sols_kept:
         ok = native.eh_verify_batch_gpu(200, 9, [a for a, _ in sols_kept], [b for _, b in sols_kept], device)
         # a GPU rejection is re-checked by the CPU verifier (reference IsValidSolution): a
         # solution only counts as bad when both reject it; a disagreement is reported
         for (st_, sol), v in zip(sols_kept, ok):
             if v:
                 continue
-            if native.eh_is_valid_solution(200, 9, st_, sol):
+            if native.eh_is_valid_solution(200, 9, st_, sol)[0]:  # (ok, reason)
                 gpu_cpu_disagree += 1
             else:
                 nbad += 1
@@ -305,6 +366,7 @@ def run(args, world):
                 "solvers_in_flight": nsolv,
                 "nonces_per_sec": round(nonces / max_dt, 2),
                 "solutions_per_nonce": round(per_nonce, 3),
+                "full": bool(args.full),
                 "verified": verified,
                 "verified_solutions": int(total_sols) if verified else 0,
                 "gpu_cpu_verifier_disagreements": gpu_cpu_disagree,

@@ -680,15 +680,24 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         uint32_t x0 = rows[i * WI] ^ rows[j * WI];
         if constexpr (WI == 1) x0 &= ~RMI;
         // identical subtrees are dropped; word 0 differs in all but ~2^-21 of the pairs, so the
-        // remaining words are read only when it matches
+        // remaining words are read only when it matches. The branch is wave-uniform (every active
+        // lane reads them when one lane's word 0 matches) and `keep` is assigned once. Written as
+        // a per-lane `if (!keep) keep |= ...`, hipcc (ROCm 7.2.0, gfx950, this file's flags) compiled
+        // the first unrolled filter instance of (200,9) rounds 3, 4, 6, 7, 8 so that every lane
+        // on this path left pv = NIL while the kept ones still counted in hist_: about one pair per
+        // nonce and round (destination bucket 0) was claimed but never emitted, its slot kept an
+        // earlier batch's row, and a stale pair-table entry was emitted into another bucket.
+        // 3 of 108,017 solutions were invalid that way; 0 of 270,706 with this form.
         bool keep = x0 != 0;
-        if (!keep) {
+        if (__builtin_amdgcn_ballot_w64(!keep) != 0) {
+            uint32_t acc = x0;
 #pragma unroll
             for (int w = 1; w < WI; ++w) {
                 uint32_t y = rows[i * WI + w] ^ rows[j * WI + w];
                 if (w == WI - 1) y &= ~RMI;
-                keep |= y != 0;
+                acc |= y;
             }
+            keep = acc != 0;
         }
         if constexpr (PRUNE) {
             if (keep && shares_parent(i, j)) keep = false;

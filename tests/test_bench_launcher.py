@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -56,6 +58,63 @@ def test_world_size_must_match():
                        env=_env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), timeout=240)
     assert p.returncode != 0
     assert "WORLD_SIZE=2" in p.stderr
+
+
+def test_plain_run_options_and_dump_layout(tmp_path):
+    """--full is off by default (a plain run skips the re-verification); --dump-outputs writes
+    float32 arrays with each nonce's solutions in lexicographic order, whatever order they came in."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    s0, s1, s2 = bytes([9] * 6), bytes([1, 2, 3, 4, 5, 6]), bytes([1, 2, 3, 4, 5, 7])
+    for order in ([s0, s1], [s1, s0]):
+        bench.dump_outputs(str(tmp_path), [order, [], [s2]])
+        got = {n: np.load(tmp_path / f"{n}.npy") for n in ("solutions_per_nonce", "solution_nonce", "solutions")}
+        assert all(v.dtype == np.float32 for v in got.values())
+        assert got["solutions_per_nonce"].tolist() == [2, 0, 1]
+        assert got["solution_nonce"].tolist() == [0, 0, 2]
+        assert got["solutions"].tolist() == [list(s1), list(s0), list(s2)]
+    bench.dump_outputs(str(tmp_path / "r"), [[], []], rank=1)
+    assert np.load(tmp_path / "r" / "solutions_rank1.npy").shape == (0, 0)
+    assert np.load(tmp_path / "r" / "solutions_per_nonce_rank1.npy").tolist() == [0, 0]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step(tmp_path):
+    """A small plain run (2 steps of 16 nonces; 74 solutions, well over the 1.85 per nonce floor):
+    --steps sets the timed steps, ms_per_step is reported, and the dump holds exactly the
+    solutions of the last timed step's inputs, each valid under the CPU consensus verifier."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from bitcoincashplus_amd import native
+    batch, steps = 16, 2
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--batch", str(batch), "--steps", str(steps),
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                       env=_env(), timeout=240)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and out["config"]["full"] is False
+    assert out["config"]["verified"] is None  # the re-verification belongs to --full
+    assert abs(out["value"] * out["ms_per_step"] * steps / 1000
+               - out["config"]["solutions_per_nonce"] * batch * steps) < 0.5
+    counts = np.load(tmp_path / "solutions_per_nonce.npy")
+    slots = np.load(tmp_path / "solution_nonce.npy")
+    sols = np.load(tmp_path / "solutions.npy")
+    assert counts.dtype == slots.dtype == sols.dtype == np.float32
+    assert counts.shape == (batch,) and sols.shape == (len(slots), 1344) and counts.sum() == len(slots)
+    states = bench.step_states(native, batch, steps - 1)
+    want = native.EquihashGpuSolver(200, 9, batch, 0).solve(states)
+    assert counts.tolist() == [len(w) for w in want]
+    assert slots.tolist() == [b for b, w in enumerate(want) for _ in w]
+    got = [bytes(r) for r in sols.astype(np.uint8)]
+    assert got == [s for w in want for s in sorted(w)]
+    for b, s in zip(slots.astype(int), got):
+        assert native.eh_is_valid_solution(200, 9, states[b], s)[0]
 
 
 def test_launch_command_shape():

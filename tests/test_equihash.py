@@ -217,6 +217,34 @@ def test_gpu_solver_200_9_no_overflow(native):
 
 
 @pytest.mark.gpu
+def test_gpu_solver_200_9_every_claimed_slot_written(native):
+    """In every bucket area of every stage the written slots are one prefix: a round emits a row
+    into each slot it claims. The inputs are the benchmark's step 5 at 8 nonces per batch, where
+    a pair filter that counted a kept pair with equal first words but never placed it left three
+    claimed slots of nonce 0 unwritten (bucket 0 of stages 4, 6 and 8); such a slot keeps an
+    earlier batch's row, and 3 of 108,017 solutions were invalid that way."""
+    import numpy as np
+    k, nb, area = 9, 512, 6016
+    header = bytes((i * 37 + 11) & 0xFF for i in range(108))
+    states = []
+    for b in range(8):
+        st = native.EquihashState(200, 9)
+        st.update(header + struct.pack("<QQQQ", 5 * 8 + b, 0, 0, 0))
+        states.append(st)
+    solver = native.EquihashGpuSolver(200, 9, 8)
+    solver.set_debug(True)
+    solver.solve(states)
+    dump = np.asarray(solver.debug_dump(), dtype=np.uint64).reshape(k, nb, area)
+    pos = np.arange(area)[None, :]
+    for stage in range(k):
+        written = dump[stage] != np.uint64(0xFFFFFFFF if stage == 0 else (1 << 64) - 1)
+        assert written.sum() > nb * area // 2, stage
+        last = (written * pos).max(axis=1)
+        holes = np.argwhere(~written & (pos < last[:, None]))
+        assert len(holes) == 0, (stage, holes[:8].tolist())
+
+
+@pytest.mark.gpu
 def test_gpu_solver_recall_small(native):
     """(48,5) / (96,5): GPU recall >= 0.97 of the CPU solver over 64 nonces."""
     for n, k in [(48, 5), (96, 5)]:

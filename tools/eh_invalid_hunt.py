@@ -84,13 +84,13 @@ def main():
         if flat:  # the GPU batch verifier's verdicts against the CPU verifier's
             gv = native.eh_verify_batch_gpu(N, K, [x for x, _ in flat], [y for _, y in flat], 0)
             for (st_, sol), v in zip(flat, gv):
-                if bool(v) != bool(native.eh_is_valid_solution(N, K, st_, sol)):
+                if bool(v) != native.eh_is_valid_solution(N, K, st_, sol)[0]:  # (ok, reason)
                     gpu_disagree += 1
                     print(json.dumps({"batch": b, "gpu_verifier": bool(v), "cpu_verifier": not bool(v)}), flush=True)
         for i, sols in enumerate(res):
             for sol in sols:
                 total += 1
-                if native.eh_is_valid_solution(N, K, sts[i], sol):
+                if native.eh_is_valid_solution(N, K, sts[i], sol)[0]:
                     if a.selfcheck > 0:  # the independent model must accept what the verifier accepts
                         a.selfcheck -= 1
                         d = diagnose(hdrs[i], native.eh_indices_from_minimal(sol, CBL))

@@ -65,7 +65,7 @@ check)
   tail -n 3 "$O/pytest_gpu.log"
   timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1
   tail -n 2 "$O/smoke.log"
-  timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 > "$O/bench.log" 2>&1
+  timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 > "$O/bench.log" 2>&1
   tail -n 1 "$O/bench.log"
   timeout -k 10 300 python -u tools/eh_recall.py --nonces 32 --threads 16 --json "$O/recall.json" > "$O/recall.log" 2>&1
   tail -n 4 "$O/recall.log"
@@ -191,7 +191,7 @@ baseline)
   tail -n 20 "$O/bench_bcp.log" ;;
 multirank)
   BCP_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 2 --batch 48 > "$O/bench2.log" 2>&1  # two ranks share one GPU: half the default batch each
+    --master-port 29533 bench.py --full --gpus 2 --steps 10 --warmup 2 --batch 48 > "$O/bench2.log" 2>&1  # two ranks share one GPU: half the default batch each
   tail -n 1 "$O/bench2.log" ;;
 *)
   echo "unknown mode $MODE"; exit 2 ;;
