@@ -276,6 +276,52 @@ __device__ __forceinline__ void eh_hash_g_hdr_from(const uint64_t P[16], const E
     out[7] = xor3_64(bs.h[7], v7, v15);
 }
 
+// eh_hash_g_hdr_from in resumable form: the 16 state words stay in registers between the calls,
+// so a caller can stop at any round boundary, do other work (or wait at a barrier) and go on.
+// begin() finishes round 0 from the uniform prefix, rounds<R0, R1>() runs rounds R0..R1-1
+// (1 <= R0 <= R1 <= 12), finish() gives the chaining words. begin, rounds<1, 12>, finish
+// compute exactly what eh_hash_g_hdr_from does.
+struct EhHdrHash {
+    uint64_t v[16];
+    uint64_t m1;
+    __device__ __forceinline__ void begin(const uint64_t P[16], const EhBaseState& bs, uint32_t g) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = P[i];
+        m1 = bs.m[1] | ((uint64_t)g << 32);
+        v[0] = ((uint64_t)((uint32_t)(v[0] >> 32) + g) << 32) | (uint32_t)v[0];
+        v[12] = rotr64(v[12] ^ v[0], 16);
+        v[8] = add64(v[8], v[12]);
+        v[4] = rotr64(v[4] ^ v[8], 63);
+        BCPK_B2G(v[0], v[5], v[10], v[15], 0, 0);
+        BCPK_B2G(v[1], v[6], v[11], v[12], 0, 0);
+        BCPK_B2G(v[2], v[7], v[8], v[13], 0, 0);
+        BCPK_B2G(v[3], v[4], v[9], v[14], 0, 0);
+    }
+    template <int R0, int R1> __device__ __forceinline__ void rounds(const EhBaseState& bs) {
+        static_assert(R0 >= 1 && R0 <= R1 && R1 <= 12, "round slice");
+        uint64_t m[16];
+        m[0] = bs.m[0];
+        m[1] = m1;
+#pragma unroll
+        for (int i = 2; i < 16; ++i) m[i] = 0;
+#pragma unroll
+        for (int r = R0; r < R1; ++r) {
+            BCPK_B2G(v[0], v[4], v[8], v[12], m[kB2Sigma[r][0]], m[kB2Sigma[r][1]]);
+            BCPK_B2G(v[1], v[5], v[9], v[13], m[kB2Sigma[r][2]], m[kB2Sigma[r][3]]);
+            BCPK_B2G(v[2], v[6], v[10], v[14], m[kB2Sigma[r][4]], m[kB2Sigma[r][5]]);
+            BCPK_B2G(v[3], v[7], v[11], v[15], m[kB2Sigma[r][6]], m[kB2Sigma[r][7]]);
+            BCPK_B2G(v[0], v[5], v[10], v[15], m[kB2Sigma[r][8]], m[kB2Sigma[r][9]]);
+            BCPK_B2G(v[1], v[6], v[11], v[12], m[kB2Sigma[r][10]], m[kB2Sigma[r][11]]);
+            BCPK_B2G(v[2], v[7], v[8], v[13], m[kB2Sigma[r][12]], m[kB2Sigma[r][13]]);
+            BCPK_B2G(v[3], v[4], v[9], v[14], m[kB2Sigma[r][14]], m[kB2Sigma[r][15]]);
+        }
+    }
+    __device__ __forceinline__ void finish(const EhBaseState& bs, uint64_t out[8]) const {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) out[i] = xor3_64(bs.h[i], v[i], v[i + 8]);
+    }
+};
+
 // Byte k (0-based) of the digest held in 8 little-endian words.
 __device__ __forceinline__ uint32_t digest_byte(const uint64_t h[8], int k) {
     return (uint32_t)(h[k >> 3] >> ((k & 7) * 8)) & 0xff;

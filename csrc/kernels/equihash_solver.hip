@@ -28,6 +28,14 @@
 //    and rejects repeated indices (LDS bitonic sort).
 //  * Block scans use DPP row shifts/broadcasts inside a wave and one LDS word per wave
 //    across waves: two barriers per scan, no ds_bpermute traffic.
+//  * Generation (VALU-bound, HBM idle) is hidden inside the collision rounds (memory- and
+//    LDS-bound, VALU mostly idle). A launch is split into nonce groups; the stand-alone kernel
+//    generates group 0 only, and the round workgroups of rounds 1..K-1 of every group give GW
+//    of their waves to the generation of the next group (eh_carry_gen): nonce n's buckets hash
+//    the chunks of nonce n + group size. Both kinds of wave meet at the round's own workgroup
+//    barriers, the same number on either path; nothing waits across workgroups. The dispatcher
+//    would not co-schedule separate generation and round kernels on a CU (profiles/equihash_r5.md);
+//    inside one workgroup the placement is given. profiles/equihash_r7.md has the measurements.
 //
 // Memory layout: every stage has its own slot array and a stage-s slot holds the row followed by
 // its parent word(s), so the emit writes one contiguous slot per output row and a pruning round
@@ -73,6 +81,12 @@
 #ifndef BCP_EH_MP_LATE_FROM
 #define BCP_EH_MP_LATE_FROM 8
 #endif
+#ifndef BCP_EH_GW // (200,9) generation waves of a carrying round workgroup (the round keeps 1024 - 64*GW threads)
+#define BCP_EH_GW 4
+#endif
+#ifndef BCP_EH_GROUPS_DEFAULT // nonce groups of a solver by its batch size (BCP_EH_GROUPS overrides at run time):
+#define BCP_EH_GROUPS_DEFAULT(batch) ((batch) >= 48 ? (batch) / 24 : 1) // groups of 24 nonces; measured at 96 (profiles/equihash_r7.md)
+#endif
 
 namespace bcpk {
 
@@ -81,7 +95,7 @@ namespace bcpk {
 // the LDS budget must allow. GENWG/NTG: LDS-sorted generation geometry; GNT x GHPT: register
 // generation (threads x hashes per thread; 0 = use the LDS-sorted kernel).
 template <int N_, int K_, int BB_, int CAP_, int NT_, int GENWG_, int NTG_, int MAXCAND_, int CAP4_ = CAP_,
-          int CAP3_ = CAP_, int WGCU_ = 1, int GNT_ = 512, int GHPT_ = 2, int CAPF_ = 0, int MPX_ = 0>
+          int CAP3_ = CAP_, int WGCU_ = 1, int GNT_ = 512, int GHPT_ = 2, int CAPF_ = 0, int MPX_ = 0, int GW_ = 0>
 struct EhCfg {
     static constexpr int N = N_, K = K_;
     static constexpr int DB = N / (K + 1);           // digit bits
@@ -105,6 +119,10 @@ struct EhCfg {
     static constexpr int AREA = AREA_NF > CAPF ? AREA_NF : CAPF;
     static constexpr int NT = NT_;                   // threads per round workgroup
     static constexpr int NW = NT_ / 64;
+    // GW: generation waves a carrying collision round (eh_round with CARRY) runs beside its
+    // NT - 64*GW round threads; 0 = the configuration never carries generation
+    static constexpr int GW = GW_;
+    static constexpr int RNT = NT_ - 64 * GW_;       // round threads of a carrying round
     static constexpr int WGCU = WGCU_;
     static constexpr int LDS_BUDGET = 160 * 1024 / WGCU_;
     static constexpr int INIT = 1 << (DB + 1);
@@ -145,6 +163,7 @@ struct EhCfg {
     static_assert(NT_ % 64 == 0 && NT_ <= 1024 && (NB <= NT_ || NB % NT_ == 0) && NB <= NTG_ && NT_ / 64 <= 64,
                   "workgroup shape");
     static_assert(words(K - 1) == 1, "final round keeps whole rows in one LDS word");
+    static_assert(GW_ == 0 || (WGCU_ == 1 && RNT >= 128 && (NB <= RNT || NB % RNT == 0)), "carrying workgroup shape");
 };
 
 // Mainnet/testnet (200,9): 512 buckets x ~4096 rows, one 1024-thread round workgroup per CU;
@@ -152,12 +171,12 @@ struct EhCfg {
 #ifndef BCP_EH_CAPF // (200,9) final-round capacity (rows per bucket; the stage areas grow to match)
 #define BCP_EH_CAPF 6016 // 5120 overflowed by 2-140 rows in ~12 buckets per 32 nonces (recall_base.json, round 5); 6016 keeps two final-round WGs per CU
 #endif
-using Cfg200_9 = EhCfg<200, 9, 9, 4416, 1024, 512, 1024, 256, 4864, 5120, 1, BCP_EH_GEN_NT, BCP_EH_GEN_HPT, BCP_EH_CAPF>;
+using Cfg200_9 = EhCfg<200, 9, 9, 4416, 1024, 512, 1024, 256, 4864, 5120, 1, BCP_EH_GEN_NT, BCP_EH_GEN_HPT, BCP_EH_CAPF, 0, BCP_EH_GW>;
 // (96,5): one extra pair slot per lane. ~1024 rows per bucket over 512 keys make ~1024 pairs, and
 // a list of 1280 overflowed in some bucket of most nonces: 84 + 18 + 36 + ~80 pairs per 16 nonces
 // in rounds 1-4, which pairs depending on the atomics' order, so a solution was lost now and then
 // (tools/eh_crosscheck.py --n 96 --k 5, profiles/equihash_r6.md).
-using Cfg96_5 = EhCfg<96, 5, 7, 1280, 256, 256, 256, 256, 1280, 1280, 1, 512, 2, 0, 1>;
+using Cfg96_5 = EhCfg<96, 5, 7, 1280, 256, 256, 256, 256, 1280, 1280, 1, 512, 2, 0, 1, 1>;
 using Cfg48_5 = EhCfg<48, 5, 3, 512, 64, 8, 64, 256>; // 512-slot areas: 8 pairs per lane (a 256-pair list overflowed on duplicate-heavy nonces)
 
 constexpr uint32_t NIL = 0xffffffffu;
@@ -553,31 +572,245 @@ template <class C> constexpr int un_walk_list(int cap) { return un_walk_bend<C>(
 // Pairs per lane: one lane per LDS row slot, plus the configuration's MPX, plus BCP_EH_MP_LATE
 // extra from round BCP_EH_MP_LATE_FROM on ((200,9) only): without depth-1 pruning the late rounds'
 // pair lists grow past the row count (duplicate subtrees) and overflowed in round 8.
-template <class C> constexpr int round_mp(int stage) {
+// Round threads of a round workgroup: all NT, or NT - 64*GW in a round that carries generation
+// (the final round never carries: two of its workgroups share a CU and the generation tables
+// would not fit).
+template <class C> constexpr int round_nt(int stage, bool carry) { return carry && stage < C::K ? C::RNT : C::NT; }
+template <class C> constexpr int round_mp(int stage, bool carry = false) {
+    const int nt = round_nt<C>(stage, carry);
     return stage == C::K ? 1
-                         : (C::AREA_NF + C::NT - 1) / C::NT + C::MPX +
+                         : (C::AREA_NF + nt - 1) / nt + C::MPX +
                                (C::K == 9 && stage >= BCP_EH_MP_LATE_FROM ? BCP_EH_MP_LATE : 0);
 }
-template <class C> constexpr int round_un(int stage) {
+template <class C> constexpr int round_un(int stage, bool carry = false) {
     const int cap = C::cap(stage);
     if (stage == C::K) return un_walk_list<C>(cap); // final round: sidx and bend only
-    const int walk = un_walk_list<C>(cap) + round_mp<C>(stage) * C::NT * 4; // + the pair list
-    const int pairs = round_mp<C>(stage) * C::NT * 4; // spair: every pair a lane may hold
+    const int pairs = round_mp<C>(stage, carry) * round_nt<C>(stage, carry) * 4; // spair: every pair a lane may hold
+    const int walk = un_walk_list<C>(cap) + pairs; // + the pair list
     return walk > pairs ? walk : pairs;
 }
-template <class C> constexpr int round_lds(int stage, bool prune) {
+// (a carrying round adds the generation waves' two NB-entry tables and the round-0 prefix)
+template <class C> constexpr int round_lds(int stage, bool prune, bool carry = false) {
     const int WR = C::words(stage - 1);
     const int WI = WR; // LDS words per row
     const int cap = C::cap(stage);
     const int pruneb = prune ? cap * 4 + (C::cp(stage - 1) ? 0 : (cap * 2 + 3) / 4 * 4) : 0;
     const int hists = stage == C::K ? 12 : 2 * C::HW * 4 + (C::NB * (C::H16 ? 2 : 4) + 3) / 4 * 4;
-    return (cap * WI + 3) / 4 * 16 + pruneb + 4 + round_un<C>(stage) + hists + (C::NW + 1) * 4;
+    const int gen = carry ? 2 * C::NB * 4 + 16 * 8 : 0;
+    return (cap * WI + 3) / 4 * 16 + pruneb + 4 + round_un<C>(stage, carry) + hists +
+           (round_nt<C>(stage, carry) / 64 + 1) * 4 + gen;
 }
 // Depth-1 duplicate pruning wherever its parent words fit next to the full rows.
-template <class C> constexpr bool round_prunes(int stage) {
+template <class C> constexpr bool round_prunes(int stage, bool carry = false) {
     // (the pruning start was measured on (200,9); the small configurations keep pruning from round 2)
     constexpr int from = C::K == 9 ? BCP_EH_PRUNE_FROM : 2;
-    return (stage >= from || stage == C::K) && stage >= 2 && round_lds<C>(stage, true) <= C::LDS_BUDGET;
+    return (stage >= from || stage == C::K) && stage >= 2 && round_lds<C>(stage, true, carry) <= C::LDS_BUDGET;
+}
+
+// Generation carried by the collision rounds of the previous nonce group. The (K-1)*NB bucket
+// iterations that rounds 1..K-1 spend on a nonce hash that nonce's partner in the next group:
+// bucket d of round S generates chunk (S-1)*NB + d, CH consecutive hashes, HB per generation thread.
+template <class C> struct GenCarry {
+    static constexpr int GT = C::GW > 0 ? 64 * C::GW : 64;       // generation threads
+    static constexpr int NHASH = (C::INIT + C::IPH - 1) / C::IPH; // hashes per nonce
+    static constexpr int ITERS = (C::K - 1) * C::NB;
+    static constexpr int HB = ((NHASH + ITERS - 1) / ITERS + GT - 1) / GT;
+    static constexpr int CH = HB * GT;
+    static constexpr int RPT = HB * C::IPH;                       // rows per thread per chunk
+    static constexpr int BPT = (C::NB + GT - 1) / GT;             // run claims per thread
+    static_assert((long long)CH * ITERS >= NHASH, "the carrying rounds cover every hash");
+};
+// What a carrying round needs of the next group (all pointers already at that group's first nonce).
+struct EhCarry {
+    const EhBaseState* states;
+    uint32_t* R0;
+    uint32_t* LEAF;
+    uint32_t* CTR0;
+    int nonces; // partner nonces that exist (the last group may be smaller)
+};
+
+// Workgroup barrier k of a carrying round's bucket iteration. The round waves and the generation
+// waves run different code between the SAME number of barriers: each path executes eh_bar<1> ..
+// eh_bar<EH_NBAR> exactly once per bucket, in order, and one prologue barrier before the loop. The two
+// barriers inside block_exscan are written out at its call sites as EH_BAR_SCAN(k) (a check
+// only; block_exscan executes them).
+constexpr int EH_NBAR = 10;
+constexpr int EH_SCAN_BARS = 2; // block_exscan with more than one wave
+template <int K> __device__ __forceinline__ void eh_bar() {
+    static_assert(K >= 1 && K <= EH_NBAR, "barrier outside the bucket iteration's count");
+    __syncthreads();
+}
+#define EH_BAR_SCAN(k) static_assert((k) >= 1 && (k) + EH_SCAN_BARS - 1 <= EH_NBAR, "scan barriers")
+
+// The generation waves of a carrying round (threads C::RNT.. of the workgroup). They walk the
+// same buckets as the round waves (the same xcd_bucket sequence, so the same trip count) and in
+// bucket (nonce n, d) generate chunk (STAGE-1)*NB + d of the next group's nonce n: what eh_gen_reg
+// does for a workgroup's rows, cut into slices between the round's barriers. The slices follow
+// the length of the round waves' intervals (profiles/equihash_r6.md, per-bucket cycles), so that
+// the generation waves are not the last to reach a barrier —
+//   before barrier 1 (commit), 4 (key placement), 5 (pair listing), 6 (pair filter): BLAKE2b
+//   rounds; nothing inside the round's two block scans (barriers 2, 3 and 7, 8 are a few hundred
+//   cycles apart); before 5 also one lane's round-0 prefix when the next bucket is another nonce's;
+//   before 6 also digest -> rows and the LDS histogram (each row's rank in this chunk's run of
+//   its bucket);
+//   before 7: one atomicAdd per non-empty destination claims the run on CTR0 (the returns are
+//   read two barriers later, so their latency is not waited for at a barrier);
+//   before 8: the histogram is cleared for the next chunk;
+//   before 9: run bases to LDS;
+//   before 10 (emit, the round's longest interval): the rows and their leaf indices go to the
+//   claimed runs, then the NEXT bucket's hashes start (the state words stay in registers).
+// A bucket whose partner nonce does not exist or whose chunk lies past the nonce's last hash
+// only keeps the barriers.
+template <class C, int STAGE>
+__device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_t* ghist, uint32_t* gbase, uint64_t* gr0p) {
+    using GC = GenCarry<C>;
+    constexpr int W0 = C::words(0);
+    constexpr int SW = (C::N + 31) / 32 + 1;
+    constexpr int SW0 = C::sw(0);
+    constexpr int GT = GC::GT, HB = GC::HB;
+    constexpr uint32_t OCAP = C::cap(1);
+    const int gtid = (int)threadIdx.x - C::RNT;
+    const int G = gridDim.x;
+    // chunk of bucket b, or -1 when there is nothing to generate (uniform)
+    auto chunk_of = [&](int b) -> int {
+        const int nonce = b / C::NB, c = (STAGE - 1) * C::NB + b % C::NB;
+        return (nonce < cy.nonces && (long long)c * GC::CH < GC::NHASH) ? c : -1;
+    };
+    auto prefix = [&](int b) { // the round-0 prefix of bucket b's partner nonce
+        if (gtid == 0 && b / C::NB < cy.nonces) {
+            uint64_t P[16];
+            eh_hdr_round0_uniform(cy.states[b / C::NB], P);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gr0p[i] = P[i];
+        }
+    };
+    // BLAKE2b round at which each slice stops (round 0 belongs to begin())
+    // in the round's emit / commit / key placement / pair listing interval; the pair filter
+    // interval takes the rest (the schedules measured are in profiles/equihash_r7.md)
+    constexpr int RA = 3, RB = 5, RC = 6, RD = 10;
+    EhHdrHash hs[HB];
+    // start the hashes of bucket b's chunk: begin() and rounds 1..RA-1
+    auto start = [&](int b) {
+        const int c = chunk_of(b);
+        if (c < 0) return;
+        const EhBaseState& bs = cy.states[b / C::NB];
+        uint64_t P[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) P[i] = gr0p[i];
+#pragma unroll
+        for (int hh = 0; hh < HB; ++hh) {
+            hs[hh].begin(P, bs, (uint32_t)c * GC::CH + (uint32_t)(hh * GT + gtid));
+            hs[hh].template rounds<1, RA>(bs);
+        }
+    };
+    int it = 0;
+    int bk = xcd_bucket<C::NB>(blockIdx.x, 0, G, nbk); // >= 0: the caller returned otherwise
+    for (int i = gtid; i < C::NB; i += GT) ghist[i] = 0;
+    prefix(bk);
+    __syncthreads(); // the prologue barrier
+    start(bk);
+    for (;;) {
+        const int nonce = bk / C::NB;
+        const int chunk = chunk_of(bk);
+        const bool act = chunk >= 0; // uniform
+        const EhBaseState& bs = cy.states[act ? nonce : 0];
+        const int bn = xcd_bucket<C::NB>(blockIdx.x, it + 1, G, nbk);
+        const bool more = bn >= 0; // uniform, the round waves' loop-exit test
+        const uint32_t g0 = (uint32_t)chunk * GC::CH + (uint32_t)gtid;
+        uint32_t rw[GC::RPT][W0];
+        uint32_t rk[GC::RPT]; // (rank within this chunk's run << 16) | bucket; NIL: no such row
+        uint32_t myb[GC::BPT];
+        if (act) {
+#pragma unroll
+            for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RA, RB>(bs);
+        }
+        eh_bar<1>();
+        eh_bar<2>(); // (the round waves are inside their key scan: two short intervals)
+        eh_bar<3>();
+        if (act) {
+#pragma unroll
+            for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RB, RC>(bs);
+        }
+        eh_bar<4>();
+        if (act) {
+#pragma unroll
+            for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RC, RD>(bs);
+        }
+        // the next bucket's prefix, when its nonce is another one: gr0p is read only in start()
+        // (before barrier 10 of the previous bucket; next after barrier 9 of this one)
+        if (more && bn / C::NB != nonce) prefix(bn);
+        eh_bar<5>();
+        if (act) {
+#pragma unroll
+            for (int hh = 0; hh < HB; ++hh) {
+                hs[hh].template rounds<RD, 12>(bs);
+                uint64_t h[8];
+                hs[hh].finish(bs, h);
+                const uint32_t g = g0 + hh * GT;
+#pragma unroll
+                for (int s = 0; s < C::IPH; ++s) {
+                    uint32_t S[SW];
+#pragma unroll
+                    for (int w = 0; w < SW; ++w) {
+                        uint32_t v = 0;
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const int k = 4 * w + t;
+                            v = (v << 8) | ((k < C::NBYTES) ? digest_byte(h, s * C::NBYTES + k) : 0u);
+                        }
+                        S[w] = v;
+                    }
+                    const int q = hh * C::IPH + s;
+                    const uint32_t d = S[0] >> (32 - C::BB);
+#pragma unroll
+                    for (int w = 0; w < W0; ++w) rw[q][w] = (S[w] << C::BB) | (S[w + 1] >> (32 - C::BB));
+                    rk[q] = NIL;
+                    if (g * C::IPH + s < (uint32_t)C::INIT) rk[q] = (atomicAdd(&ghist[d], 1u) << 16) | d;
+                }
+            }
+        }
+        eh_bar<6>();
+        if (act) {
+#pragma unroll
+            for (int k = 0; k < GC::BPT; ++k) {
+                const int b = gtid + k * GT;
+                const uint32_t c = b < C::NB ? ghist[b] : 0u;
+                myb[k] = 0;
+                if (c) myb[k] = atomicAdd(&cy.CTR0[(size_t)nonce * C::NB + b], c);
+            }
+        }
+        eh_bar<7>();
+        if (act)
+            for (int i = gtid; i < C::NB; i += GT) ghist[i] = 0;
+        eh_bar<8>();
+        if (act) {
+#pragma unroll
+            for (int k = 0; k < GC::BPT; ++k) {
+                const int b = gtid + k * GT;
+                if (b < C::NB) gbase[b] = myb[k];
+            }
+        }
+        eh_bar<9>();
+        if (act) {
+            const auto rs = buf_rsrc(cy.R0 + (size_t)nonce * C::ROWS * SW0, (uint32_t)(C::ROWS * SW0 * 4));
+            const auto rl = buf_rsrc(cy.LEAF + (size_t)nonce * C::ROWS, (uint32_t)(C::ROWS * 4));
+#pragma unroll
+            for (int q = 0; q < GC::RPT; ++q) {
+                const uint32_t d = rk[q] & 0xffff;
+                const uint32_t pos = gbase[d < (uint32_t)C::NB ? d : 0] + (rk[q] >> 16);
+                const uint32_t slot = d * C::AREA + pos;
+                const bool ok = rk[q] != NIL && pos < OCAP;
+                const uint32_t li = (g0 + (q / C::IPH) * GT) * C::IPH + (q % C::IPH); // leaf index
+                row_store<W0>(rs, ok ? slot * (SW0 * 4) : OOB, rw[q]);
+                __builtin_amdgcn_raw_buffer_store_b32(li, rl, ok ? slot * 4 : OOB, 0, 0);
+            }
+        }
+        if (more) start(bn); // the round waves' emit is their longest interval
+        eh_bar<EH_NBAR>();
+        if (!more) break;
+        bk = bn;
+        ++it;
+    }
 }
 
 // STAGE < K: collision round producing stage-STAGE rows. STAGE == K: final round.
@@ -602,23 +835,32 @@ template <class C> constexpr bool round_prunes(int stage) {
 // equal on all remaining bits.
 // Input rows whose slots carry compact parents keep the parent-bucket bits in their padding in
 // LDS (the prune check reads them); every comparison and the emit XOR mask them out (RMI).
-// pdrop[STAGE]: pairs lost to a full pair list or to the 14-partner cap of a row in a large key
+// pdrop holds 2K + 2 counters per nonce. pdrop[STAGE]: pairs lost to a full pair list or to the 14-partner cap of a row in a large key
 // group (duplicate subtrees); pdrop[K + STAGE]: stage-(STAGE-1) rows past the
 // round's capacity (offered to a bucket but never read), counted for every nonce.
-template <class C, int STAGE, bool STAMP>
+//
+// CARRY (collision rounds of a configuration with GW > 0): the last GW waves of the workgroup are
+// generation waves. The first C::RNT threads run the round exactly as described above (every
+// per-workgroup size below is taken from that thread count); the generation waves run
+// eh_carry_gen between the same workgroup barriers.
+template <class C, int STAGE, bool STAMP, bool CARRY = false>
 __global__ __launch_bounds__(C::NT) __attribute__((amdgpu_waves_per_eu(C::WGCU * C::NT / 256)))
 void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTRin, uint32_t* __restrict__ Rout,
               uint32_t* __restrict__ CTRout, uint32_t* __restrict__ ncand, uint64_t* __restrict__ cand,
-              uint64_t* __restrict__ stamps, uint32_t* __restrict__ pdrop, int nbk) {
+              uint64_t* __restrict__ stamps, uint32_t* __restrict__ pdrop, int nbk, EhCarry carry) {
     constexpr int WI = C::words(STAGE - 1);
     constexpr int WO = (STAGE < C::K) ? C::words(STAGE) : 1;
     constexpr int CAP = C::cap(STAGE);                        // LDS rows / pair-list entries
     constexpr bool FINAL = STAGE == C::K;
-    constexpr bool PRUNE = round_prunes<C>(STAGE);
-    static_assert(round_lds<C>(STAGE, PRUNE) <= 160 * 1024 / C::WGCU, "round LDS budget");
-    constexpr int NT = C::NT;
+    constexpr int PDW = 2 * C::K + 2;                         // drop counters per nonce
+    static_assert(!CARRY || (C::GW > 0 && !FINAL && !STAMP), "only plain collision rounds carry generation");
+    constexpr bool PRUNE = round_prunes<C>(STAGE, CARRY);
+    static_assert(PRUNE == round_prunes<C>(STAGE), "a carrying round prunes like the plain one");
+    static_assert(round_lds<C>(STAGE, PRUNE, CARRY) <= 160 * 1024 / C::WGCU, "round LDS budget");
+    constexpr int NT = round_nt<C>(STAGE, CARRY);           // round threads
+    static_assert(!CARRY || NT / 64 > 1, "block_exscan runs its two barriers only with more than one wave");
     constexpr int RPL = (CAP + NT - 1) / NT;                // prefetched rows per lane
-    constexpr int MP = round_mp<C>(STAGE);                  // pairs per lane (registers)
+    constexpr int MP = round_mp<C>(STAGE, CARRY);           // pairs per lane (registers)
     constexpr int SWI = C::sw(STAGE - 1);                  // words per input slot
     constexpr int SWO = STAGE < C::K ? C::sw(STAGE) : 1;   // words per output slot
     constexpr bool CPI = C::cp(STAGE - 1);                 // input slots carry one compact parent word
@@ -634,10 +876,14 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     __shared__ uint32_t psig[PRUNE ? CAP : 1];                // the input rows' parent word (j << 16 | i, + d bits)
     __shared__ uint16_t pdw[PRUNE && !CPI ? CAP : 1];         // two-word parents: the producing bucket
     __shared__ uint32_t npairs;                                // wave-compaction pair list fill
-    __shared__ __attribute__((aligned(16))) uint8_t un[round_un<C>(STAGE)];
+    __shared__ __attribute__((aligned(16))) uint8_t un[round_un<C>(STAGE, CARRY)];
+    static_assert(FINAL || (sizeof(un) >= (size_t)un_walk_list<C>(CAP) + (size_t)MP * NT * 4),
+                  "the union holds sidx, bend and this round's MP * NT pairs");
     __shared__ uint32_t hist_[FINAL ? 1 : C::HW], cur_[FINAL ? 1 : C::HW]; // H16: two 16-bit counters per word
     __shared__ HT base[FINAL ? 1 : C::NB];
-    __shared__ uint32_t wsum[C::NW + 1];
+    __shared__ uint32_t wsum[NT / 64 + 1];
+    __shared__ uint32_t ghist[CARRY ? C::NB : 1], gbase[CARRY ? C::NB : 1]; // the generation waves' tables
+    __shared__ uint64_t gr0p[CARRY ? 16 : 1];
     uint16_t* sidx = reinterpret_cast<uint16_t*>(un);
     uint32_t* bend = reinterpret_cast<uint32_t*>(un + un_walk_bend<C>(CAP));
     uint32_t* plist = reinterpret_cast<uint32_t*>(un + un_walk_list<C>(CAP));
@@ -647,6 +893,13 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     int it = 0;
     int bk = xcd_bucket<C::NB>(blockIdx.x, 0, G, nbk);
     if (bk < 0) return; // uniform per workgroup
+    if constexpr (CARRY) {
+        // the role is wave-uniform: a scalar branch
+        if (__builtin_amdgcn_readfirstlane(tid >> 6) >= NT / 64) {
+            eh_carry_gen<C, STAGE>(carry, nbk, ghist, gbase, gr0p);
+            return;
+        }
+    }
 
     // histogram entry b (count or running position) and its returning increment
     auto hget = [&](const uint32_t* h, int b) -> uint32_t {
@@ -770,7 +1023,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     for (;;) {
         const int nonce = bk / C::NB, d = bk % C::NB;
         EH_STAMP(0);
-        if (tid == 0 && fill > (uint32_t)CAP) atomicAdd(&pdrop[C::K + STAGE], fill - CAP); // rare
+        if (tid == 0 && fill > (uint32_t)CAP) atomicAdd(&pdrop[nonce * PDW + C::K + STAGE], fill - CAP); // rare
         // A. commit the prefetched bucket (one row per lane per unit)
         {
             const uint32_t ot = opaque_tid();
@@ -812,7 +1065,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         const int bn2 = xcd_bucket<C::NB>(blockIdx.x, it + 2, G, nbk);
         issue(0, SLI); // nothing moves when !more (pf_n = 0), but the instruction count stays fixed
         fill_next = fill_of(bn2);
-        __syncthreads();
+        eh_bar<1>();
         EH_STAMP(2);
 
         // D1. key sort. FOLD: the commit counted the keys; scan to group starts and place each
@@ -822,6 +1075,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         auto key_of = [&](uint32_t i) -> uint32_t { return rows[i * WI] >> (32 - C::RB); };
         uint32_t kpairs[FOLD ? RPL : 1];
         if constexpr (FOLD) {
+            EH_BAR_SCAN(2); // barriers 2, 3
             block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
             const uint32_t ot = opaque_tid();
 #pragma unroll
@@ -835,7 +1089,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     sidx[pos] = (uint16_t)r;
                     krank[u] = pos;
                     kpairs[u] = min(e - pos - 1, 14u);
-                    if (e - pos - 1 > 14u) atomicAdd(&pdrop[STAGE], e - pos - 1 - 14u); // capped pairs (rare) count as pair-list drops
+                    if (e - pos - 1 > 14u) atomicAdd(&pdrop[nonce * PDW + STAGE], e - pos - 1 - 14u); // capped pairs (rare) count as pair-list drops
                 }
             }
         } else {
@@ -845,7 +1099,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             for (uint32_t i = tid; i < n; i += NT) sidx[atomicAdd(&bend[key_of(i)], 1u)] = (uint16_t)i;
         }
         issue(SLI, 2 * SLI);
-        __syncthreads();
+        eh_bar<4>();
         EH_STAMP(3);
 
         if constexpr (FINAL) {
@@ -892,11 +1146,11 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     plist[o] = ((uint32_t)sidx[q] << 16) | i;
                 }
             }
-            __syncthreads();
+            eh_bar<5>();
             EH_STAMP(7); // pair list complete (splits D2 into listing and filtering)
             const uint32_t P = npairs;
             const uint32_t Pc = min(P, (uint32_t)(MP * NT));
-            if (tid == 0 && P > (uint32_t)(MP * NT)) atomicAdd(&pdrop[STAGE], P - MP * NT); // rare
+            if (tid == 0 && P > (uint32_t)(MP * NT)) atomicAdd(&pdrop[nonce * PDW + STAGE], P - MP * NT); // rare
             uint32_t pv[MP], pd[MP];
 #pragma unroll
             for (int u = 0; u < MP; ++u) {
@@ -916,7 +1170,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             }
             // bend's last reads were before the barrier above; the next commit counts here
             for (int k = tid; k < C::NRESTS; k += NT) bend[k] = 0;
-            __syncthreads();
+            eh_bar<6>();
             EH_STAMP(4);
             // D3. claim this bucket's runs in the destination areas (device-scope atomics whose
             //     latency hides behind the scan and the scatter), then sort the pairs by
@@ -932,6 +1186,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             issue(2 * SLI, RPL); // after the claim: waiting for its return then skips these loads
             uint32_t start = 0; // first LDS slot of the thread's first destination
             uint32_t np;
+            EH_BAR_SCAN(7); // barriers 7, 8
             if constexpr (C::H16)
                 np = block_exscan<NT, BPT, uint16_t, uint16_t>(reinterpret_cast<const uint16_t*>(hist_),
                                                                reinterpret_cast<uint16_t*>(cur_), C::NB, wsum, &start);
@@ -948,7 +1203,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     start += hget(hist_, b);
                 }
             }
-            __syncthreads();
+            eh_bar<9>();
             EH_STAMP(5);
             // D4. emit, one lane per output row in destination order: XOR, shift one digit,
             //     store into the claimed run (rows past the next round's capacity are dropped)
@@ -983,7 +1238,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                 row_store<SWO>(rs_out, ok ? slot * (SWO * 4) : OOB, ov);
             }
         }
-        __syncthreads();
+        eh_bar<EH_NBAR>();
         EH_STAMP(6);
         if (!more) break;
         bk = bn;
@@ -1150,6 +1405,7 @@ struct EquihashGpuSolver::Impl {
     std::vector<bool> compact;                  // per stage: compact parent word
     int inflight = 0;
     int ncu = 1;
+    int groups = 1; // nonce groups of a launch (see launch()); 1: the whole batch is generated up front
     bool debug = false, stamp_mode = false;
     DevBuf<uint64_t> d_stamps;
     EhGpuStats stats;
@@ -1179,8 +1435,8 @@ struct EquihashGpuSolver::Impl {
         d_leaf.alloc((size_t)batch * C::ROWS);
         cp_ib = C::IB, cp_dh = C::DH, cp_dhm = C::DHM, cp_dx = C::DX, cp_rmask = C::RMASK, cp_imask = C::IMASK;
         d_ncand.alloc(batch);
-        d_pdrop.alloc(2 * C::K + 2); // [1..K]: pair-list drops per round, [K+1..2K]: row drops per stage
-        h_pdrop.alloc(2 * C::K + 2);
+        d_pdrop.alloc((size_t)batch * (2 * C::K + 2)); // per nonce, [1..K]: pair-list drops per round, [K+1..2K]: row drops per stage
+        h_pdrop.alloc((size_t)batch * (2 * C::K + 2));
         d_cand.alloc((size_t)batch * C::MAXCAND);
         d_idx.alloc((size_t)batch * C::MAXCAND * C::L);
         d_valid.alloc((size_t)batch * C::MAXCAND);
@@ -1199,32 +1455,54 @@ struct EquihashGpuSolver::Impl {
     }
 
     // Persistent round kernels: as many workgroups as fit on the device at once.
-    template <class C, int S, bool ST> int round_grid(int nbk) {
+    template <class C, int S, bool ST, bool CY> int round_grid(int nbk) {
         static int per_cu = -1;
         if (per_cu < 0) {
             int occ = 0;
-            BCP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, bcpk::eh_round<C, S, ST>, C::NT, 0));
+            BCP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, bcpk::eh_round<C, S, ST, CY>, C::NT, 0));
             per_cu = std::max(occ, 1);
         }
         return std::min(nbk, ncu * per_cu);
     }
-    template <class C, int S> void launch_round(int nstates) {
-        const uint32_t* rin = d_rst[S - 1].p;
-        uint32_t* rout = S < C::K ? d_rst[S].p : nullptr;
-        const uint32_t* cin = d_ctr.p + (size_t)(S - 1) * batch * C::NB;
-        uint32_t* cout = S < C::K ? d_ctr.p + (size_t)S * batch * C::NB : nullptr;
-        const int nbk = C::NB * nstates;
+    // Round S over the group of `gn` nonces that starts at nonce `noff`. With next > 0 (and S < K)
+    // the round carries the generation of the next group's first `next` nonces.
+    template <class C, int S> void launch_round(int noff, int gn, int next) {
+        const size_t o = (size_t)noff;
+        constexpr size_t PDW = 2 * C::K + 2;
+        const uint32_t* rin = d_rst[S - 1].p + o * C::ROWS * C::sw(S - 1);
+        uint32_t* rout = S < C::K ? d_rst[S].p + o * C::ROWS * C::sw(S < C::K ? S : 0) : nullptr;
+        const uint32_t* cin = d_ctr.p + ((size_t)(S - 1) * batch + o) * C::NB;
+        uint32_t* cout = S < C::K ? d_ctr.p + ((size_t)S * batch + o) * C::NB : nullptr;
+        uint32_t* nc = d_ncand.p + o;
+        uint64_t* cd = d_cand.p + o * C::MAXCAND;
+        const int nbk = C::NB * gn;
+        bcpk::EhCarry cy{};
+        if constexpr (C::GW > 0 && S < C::K) {
+            if (next > 0 && !stamp_mode) {
+                const size_t p = o + (size_t)gn; // the next group's first nonce
+                cy.states = d_states.p + p;
+                cy.R0 = d_rst[0].p + p * C::ROWS * C::sw(0);
+                cy.LEAF = d_leaf.p + p * C::ROWS;
+                cy.CTR0 = d_ctr.p + p * C::NB;
+                cy.nonces = next;
+                hipLaunchKernelGGL((bcpk::eh_round<C, S, false, true>), dim3(round_grid<C, S, false, true>(nbk)),
+                                   dim3(C::NT), 0, stream, rin, cin, rout, cout, nc, cd, nullptr,
+                                   d_pdrop.p + o * PDW, nbk, cy);
+                ++stats.carry_launches;
+                return;
+            }
+        }
         if (stamp_mode) {
-            uint64_t* st = d_stamps.p + (size_t)(S - 1) * batch * C::NB * 16;
-            hipLaunchKernelGGL((bcpk::eh_round<C, S, true>), dim3(round_grid<C, S, true>(nbk)), dim3(C::NT), 0,
-                               stream, rin, cin, rout, cout, d_ncand.p, d_cand.p, st, d_pdrop.p, nbk);
+            uint64_t* st = d_stamps.p + ((size_t)(S - 1) * batch + o) * C::NB * 16;
+            hipLaunchKernelGGL((bcpk::eh_round<C, S, true>), dim3(round_grid<C, S, true, false>(nbk)), dim3(C::NT), 0,
+                               stream, rin, cin, rout, cout, nc, cd, st, d_pdrop.p + o * PDW, nbk, cy);
         } else {
-            hipLaunchKernelGGL((bcpk::eh_round<C, S, false>), dim3(round_grid<C, S, false>(nbk)), dim3(C::NT), 0,
-                               stream, rin, cin, rout, cout, d_ncand.p, d_cand.p, nullptr, d_pdrop.p, nbk);
+            hipLaunchKernelGGL((bcpk::eh_round<C, S, false>), dim3(round_grid<C, S, false, false>(nbk)), dim3(C::NT), 0,
+                               stream, rin, cin, rout, cout, nc, cd, nullptr, d_pdrop.p + o * PDW, nbk, cy);
         }
     }
-    template <class C, int... S> void launch_rounds(int nstates, std::integer_sequence<int, S...>) {
-        (launch_round<C, S + 1>(nstates), ...);
+    template <class C, int... S> void launch_rounds(int noff, int gn, int next, std::integer_sequence<int, S...>) {
+        (launch_round<C, S + 1>(noff, gn, next), ...);
     }
 
     template <class C> void launch(size_t nstates) {
@@ -1248,13 +1526,23 @@ struct EquihashGpuSolver::Impl {
             hdr &= st.g_byte == 12;
             for (int w = 2; w < 16; ++w) hdr &= st.m[w] == 0;
         }
+        // Nonce groups: the stand-alone kernel generates group 0 only, and rounds 1..K-1 of every
+        // group carry the generation of the next one. One group is the whole batch generated up
+        // front (inputs that are not header-shaped, configurations without generation waves and
+        // the stamped diagnostic rounds always run that way).
+        int gsz = (int)nstates;
+        if (C::GW > 0 && hdr && !stamp_mode && groups > 1) {
+            gsz = ((int)nstates + groups - 1) / groups;
+            if (gsz >= bcpk::NXCD) gsz = (gsz + bcpk::NXCD - 1) / bcpk::NXCD * bcpk::NXCD; // keeps the XCD mapping
+        }
+        const int gen_n = std::min(gsz, (int)nstates); // nonces of the stand-alone generation
         uint32_t* r0 = d_rst[0].p;
         hipStream_t gs = stream;
         if (after) BCP_HIP_CHECK(hipStreamWaitEvent(gs, after->ev_gen, 0)); // one generation at a time
         constexpr bool reg = bcpk::GenReg<C, C::GNT, C::GHPT>::OK;
         if constexpr (reg) {
             using GR = bcpk::GenReg<C, C::GNT, C::GHPT>;
-            const int items = GR::GWG * (int)nstates;
+            const int items = GR::GWG * gen_n;
             const int grid = items;
             if (hdr)
                 hipLaunchKernelGGL((bcpk::eh_gen_reg<C, true, C::GNT, C::GHPT>), dim3(grid), dim3(C::GNT), 0, gs,
@@ -1263,14 +1551,18 @@ struct EquihashGpuSolver::Impl {
                 hipLaunchKernelGGL((bcpk::eh_gen_reg<C, false, C::GNT, C::GHPT>), dim3(grid), dim3(C::GNT), 0, gs,
                                    d_states.p, r0, d_leaf.p, d_ctr.p, items);
         } else if (hdr)
-            hipLaunchKernelGGL((bcpk::eh_gen<C, true>), dim3(C::GENWG * nstates), dim3(C::NTG), 0, gs,
+            hipLaunchKernelGGL((bcpk::eh_gen<C, true>), dim3(C::GENWG * gen_n), dim3(C::NTG), 0, gs,
                                d_states.p, r0, d_leaf.p, d_ctr.p);
         else
-            hipLaunchKernelGGL((bcpk::eh_gen<C, false>), dim3(C::GENWG * nstates), dim3(C::NTG), 0, gs,
+            hipLaunchKernelGGL((bcpk::eh_gen<C, false>), dim3(C::GENWG * gen_n), dim3(C::NTG), 0, gs,
                                d_states.p, r0, d_leaf.p, d_ctr.p);
         BCP_HIP_CHECK(hipEventRecord(ev_gen, gs));
         if (after) BCP_HIP_CHECK(hipStreamWaitEvent(stream, after->ev_rounds, 0)); // one round chain at a time
-        launch_rounds<C>((int)nstates, std::make_integer_sequence<int, C::K>{});
+        for (int noff = 0; noff < (int)nstates; noff += gsz) {
+            const int gn = std::min(gsz, (int)nstates - noff);
+            const int next = std::max(0, std::min(gsz, (int)nstates - noff - gsz));
+            launch_rounds<C>(noff, gn, next, std::make_integer_sequence<int, C::K>{});
+        }
         constexpr int EB = C::L < 64 ? 64 : C::L;
         bcpk::EhStages stages{};
         for (int s = 0; s < C::K; ++s) stages.r[s] = d_rst[s].p;
@@ -1311,6 +1603,10 @@ EquihashGpuSolver::EquihashGpuSolver(unsigned n, unsigned k, int batch, int devi
     impl->k = k;
     impl->batch = batch;
     impl->device = UseDevice(device);
+    // BCP_EH_GROUPS=n: split every launch into n nonce groups (1 = no carried generation)
+    impl->groups = BCP_EH_GROUPS_DEFAULT(batch);
+    if (const char* e = getenv("BCP_EH_GROUPS")) impl->groups = std::max(1, atoi(e));
+    impl->groups = std::min(impl->groups, batch);
     BCP_HIP_CHECK(hipDeviceGetAttribute(&impl->ncu, hipDeviceAttributeMultiprocessorCount, impl->device));
     BCP_HIP_CHECK(hipStreamCreateWithFlags(&impl->stream, hipStreamNonBlocking));
     BCP_HIP_CHECK(hipEventCreateWithFlags(&impl->ev_gen, hipEventDisableTiming));
@@ -1372,16 +1668,32 @@ std::vector<std::vector<double>> EquihashGpuSolver::PhaseCycles(int nonces) {
 }
 void EquihashGpuSolver::ResetStats() { impl->stats = EhGpuStats(); }
 
-// Debug: nonce 0 of the last batch, K arrays of ROWS slots: stage-0 leaf indices (zero-extended),
+// Debug mode: one nonce of the last batch, its bucket fill counters (rows offered to each bucket),
+// K stages of NB.
+std::vector<uint32_t> EquihashGpuSolver::DebugFills(int nonce) {
+    const Impl& m = *impl;
+    if (!m.debug || nonce < 0 || nonce >= m.batch) throw std::invalid_argument("DebugFills: debug mode and a nonce of the batch");
+    BCP_HIP_CHECK(hipSetDevice(m.device));
+    BCP_HIP_CHECK(hipStreamSynchronize(m.stream));
+    std::vector<uint32_t> out;
+    for (size_t s = 0; s < m.kstages; ++s) {
+        const uint32_t* p = m.h_ctr_all.p + (s * m.batch + nonce) * m.nb;
+        out.insert(out.end(), p, p + m.nb);
+    }
+    return out;
+}
+
+// Debug: one nonce of the last batch, K arrays of ROWS slots: stage-0 leaf indices (zero-extended),
 // then the parent triples of stages 1..K-1; with SetDebug(true) never-written slots read all-ones.
-std::vector<uint64_t> EquihashGpuSolver::DebugDump() {
+std::vector<uint64_t> EquihashGpuSolver::DebugDump(int nonce) {
+    if (nonce < 0 || nonce >= impl->batch) throw std::invalid_argument("DebugDump: nonce outside the batch");
     BCP_HIP_CHECK(hipSetDevice(impl->device));
     BCP_HIP_CHECK(hipStreamSynchronize(impl->stream));
     const Impl& m = *impl;
     const size_t R = m.rows, K = m.kstages;
     std::vector<uint64_t> out(K * R);
     std::vector<uint32_t> leaf(R);
-    BCP_HIP_CHECK(hipMemcpy(leaf.data(), m.d_leaf.p, R * 4, hipMemcpyDeviceToHost));
+    BCP_HIP_CHECK(hipMemcpy(leaf.data(), m.d_leaf.p + (size_t)nonce * R, R * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < R; ++i) out[i] = leaf[i];
     // the parent word(s) follow the row in every stage-s slot of nonce 0 (bcpk::cpack layout)
     auto cunpack_d = [&](uint32_t pw, uint32_t last) {
@@ -1391,7 +1703,7 @@ std::vector<uint64_t> EquihashGpuSolver::DebugDump() {
     for (size_t s = 1; s < K; ++s) {
         const size_t sw = m.slot_words[s], w = m.row_words[s];
         std::vector<uint32_t> buf(R * sw);
-        BCP_HIP_CHECK(hipMemcpy(buf.data(), m.d_rst[s].p, R * sw * 4, hipMemcpyDeviceToHost));
+        BCP_HIP_CHECK(hipMemcpy(buf.data(), m.d_rst[s].p + (size_t)nonce * R * sw, R * sw * 4, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < R; ++i) {
             const uint32_t* q = &buf[i * sw + w];
             if (m.compact[s] && q[0] == 0xffffffffu) // never written (SetDebug fill): no LDS row index is all-ones
@@ -1486,8 +1798,22 @@ std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Collect() {
         const size_t K = impl->kstages;
         impl->stats.pair_dropped_all.resize(K + 1, 0);
         impl->stats.stage_dropped_all.resize(K, 0);
-        for (size_t r = 0; r <= K; ++r) impl->stats.pair_dropped_all[r] += impl->h_pdrop.p[r];
-        for (size_t s = 0; s < K; ++s) impl->stats.stage_dropped_all[s] += impl->h_pdrop.p[K + 1 + s];
+        impl->stats.pair_dropped_nonce.assign(ns, 0);
+        impl->stats.stage_dropped_nonce.assign(ns, 0);
+        std::vector<uint64_t> pd(K + 1, 0);
+        for (int nn = 0; nn < ns; ++nn) {
+            const uint32_t* q = impl->h_pdrop.p + (size_t)nn * (2 * K + 2);
+            for (size_t r = 0; r <= K; ++r) {
+                pd[r] += q[r];
+                impl->stats.pair_dropped_all[r] += q[r];
+                impl->stats.pair_dropped_nonce[nn] += q[r];
+            }
+            for (size_t s = 0; s < K; ++s) {
+                impl->stats.stage_dropped_all[s] += q[K + 1 + s];
+                impl->stats.stage_dropped_nonce[nn] += q[K + 1 + s];
+            }
+        }
+        if (impl->debug) impl->stats.pair_dropped = pd;
     }
     if (impl->debug) {
         // nonce 0: per stage, rows offered to each bucket (its fill counter) vs the LDS capacity
@@ -1497,7 +1823,6 @@ std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Collect() {
         impl->stats.stage_dropped.assign(impl->kstages, 0);
         impl->stats.stage_maxfill.assign(impl->kstages, 0);
         impl->stats.stage_top.assign(impl->kstages, {});
-        impl->stats.pair_dropped.assign(impl->h_pdrop.p, impl->h_pdrop.p + impl->kstages + 1);
         // every nonce of the batch: the fullest bucket per stage and the buckets past capacity
         impl->stats.stage_maxfill_all.assign(impl->kstages, 0);
         for (size_t s = 0; s < impl->kstages; ++s)

@@ -44,11 +44,14 @@ struct EhGpuStats {
     uint64_t cand_dropped = 0;   // final-round candidates past the per-nonce list (MAXCAND), every nonce
     uint64_t cand_max = 0;       // largest per-nonce final-round candidate count seen
     double gpu_ms = 0;
+    uint64_t carry_launches = 0; // round kernels launched with generation waves (carrying the next nonce group)
     std::vector<uint64_t> stage_rows, stage_dropped, stage_maxfill; // debug mode, last batch
     std::vector<std::vector<uint64_t>> stage_top;
     std::vector<uint64_t> pair_dropped;
     std::vector<uint64_t> stage_dropped_all;  // every nonce: rows past a round's capacity per stage (accumulated)
     std::vector<uint64_t> pair_dropped_all;   // every nonce: pairs past a round's pair list, per round (accumulated)
+    std::vector<uint64_t> pair_dropped_nonce;  // last batch, per nonce: pairs dropped in all rounds
+    std::vector<uint64_t> stage_dropped_nonce; // last batch, per nonce: rows dropped in all stages
     std::vector<uint64_t> stage_maxfill_all;  // debug: fullest bucket per stage, last batch
     std::vector<uint64_t> overflow_fills; // debug: (stage << 32 | fill) of every bucket past its capacity (accumulated)
     std::vector<std::vector<uint32_t>> debug_cands;                  // debug: every candidate of nonce 0 (valid or not)
@@ -79,7 +82,8 @@ public:
     const EhGpuStats& Stats() const;
     void SetDebug(bool on);   // collect per-stage bucket statistics (extra D2H copies)
     void SetStampMode(bool on); // diagnostic: launch phase-timestamped round kernels
-    std::vector<uint64_t> DebugDump(); // diagnostic: leaf indices + parent triples of nonce 0
+    std::vector<uint64_t> DebugDump(int nonce = 0); // diagnostic: leaf indices + parent triples of one nonce of the last batch
+    std::vector<uint32_t> DebugFills(int nonce);    // debug mode: the nonce's bucket fill counters, K stages x NB
     // Test hook (after a Solve): re-run the tree expansion of nonce 0's candidates with the first
     // candidate's left stage-(K-1) parent corrupted - mode 1: bucket out of range, mode 2: LDS
     // row out of range, 0: untouched. Returns each candidate's valid flag; the expansion must

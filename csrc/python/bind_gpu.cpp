@@ -97,6 +97,7 @@ void bind_gpu(pyb::module_& m) {
                  d["cand_dropped"] = st.cand_dropped;
                  d["cand_max"] = st.cand_max;
                  d["gpu_ms"] = st.gpu_ms;
+                 d["carry_launches"] = st.carry_launches;
                  d["stage_rows"] = st.stage_rows;
                  d["stage_dropped"] = st.stage_dropped;
                  d["stage_maxfill"] = st.stage_maxfill;
@@ -104,6 +105,8 @@ void bind_gpu(pyb::module_& m) {
                  d["pair_dropped"] = st.pair_dropped;
                  d["stage_dropped_all"] = st.stage_dropped_all;
                  d["pair_dropped_all"] = st.pair_dropped_all;
+                 d["pair_dropped_nonce"] = st.pair_dropped_nonce;
+                 d["stage_dropped_nonce"] = st.stage_dropped_nonce;
                  d["stage_maxfill_all"] = st.stage_maxfill_all;
                  d["overflow_fills"] = st.overflow_fills;
                  d["debug_cands"] = st.debug_cands;
@@ -112,7 +115,8 @@ void bind_gpu(pyb::module_& m) {
         .def("reset_stats", &gpu::EquihashGpuSolver::ResetStats)
         .def("set_debug", &gpu::EquihashGpuSolver::SetDebug)
         .def("set_stamp_mode", &gpu::EquihashGpuSolver::SetStampMode)
-        .def("debug_dump", &gpu::EquihashGpuSolver::DebugDump)
+        .def("debug_dump", &gpu::EquihashGpuSolver::DebugDump, pyb::arg("nonce") = 0)
+        .def("debug_fills", &gpu::EquihashGpuSolver::DebugFills, pyb::arg("nonce"))
         .def("phase_cycles", &gpu::EquihashGpuSolver::PhaseCycles);
 
     // Multi-GPU Equihash search of the built-in miner (EquihashSearchGpu) with an accept-all target:

@@ -120,7 +120,7 @@ pmc-eh|pmc-ec)
     S="python3 $R/tools/ecdsa_bench.py ${3:-262144}"
   fi
   cd /tmp
-  pass() { local n=$1; shift; timeout -s KILL 90 rocprofv3 --kernel-trace --output-format csv -d "$O/$n" -o "$n" --pmc "$@" -- $S > "$O/$n.log" 2>&1; }
+  pass() { local n=$1; shift; timeout -s KILL 90 rocprofv3 --output-format csv -d "$O/$n" -o "$n" --pmc "$@" -- $S > "$O/$n.log" 2>&1; }
   pass a SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES
   pass b SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM
   pass c FETCH_SIZE GRBM_GUI_ACTIVE

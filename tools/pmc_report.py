@@ -29,9 +29,9 @@ SIMDS = 4 * CUS
 
 
 def kname(name):
-    m = re.search(r"eh_round<[^>]*>, (\d+), (?:false|true)>", name)
-    if m:
-        return "eh_round<%s>" % m.group(1)
+    m = re.search(r"eh_round<[^>]*>, (\d+), (?:false|true)(?:, (false|true))?>", name)
+    if m:  # (the last argument marks a round that carries generation)
+        return "eh_round<%s>%s" % (m.group(1), "+gen" if m.group(2) == "true" else "")
     for k in ("eh_gen_reg", "eh_gen", "eh_expand", "eh_verify", "ecdsa_verify_kernel", "ecdsa_verify10h_kernel",
               "ecdsa_verify10_kernel", "ecdsa_fused_kernel", "ecdsa_prep_kernel"):
         if k in name:
