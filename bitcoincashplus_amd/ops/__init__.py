@@ -21,6 +21,8 @@ Kernel map (reference hot loops):
   merkle_root        K6  whole-tree reduction on device              sha256.hip
   scan_nonces        K5  legacy SHA-256d header nonce scan           sha256.hip
   equihash_verify    K4  batched IsValidSolution                     equihash_verify.hip
+  equihash_pow_check K5  block hash + target compare of headers      equihash_pow.hip
+  equihash_mine      K1-K5 nonce states, solve, encode, hash, filter  equihash_solver.hip + equihash_pow.h
   ecdsa_verify       K8  batched secp256k1 verify                    secp256k1.hip
   verify_forkid      K8  block-path deferred checks -> verify batch  secp256k1.hip (GpuVerifyDeferred)
   short_txids        K9  BIP152 SipHash-2-4 short ids                relay.hip
@@ -118,8 +120,41 @@ def ecdsa_verify(items: Iterable, use_gpu: bool = True, threads: int = 8):
     return native.ecdsa_verify_batch([(bytes(a), bytes(b), bytes(c)) for a, b, c in items], use_gpu, threads)
 
 
+def equihash_pow_check(n: int, k: int, in140s, solutions, target, device: int = -1):
+    """Block hashes of headers given as (140-byte Equihash input, minimal solution) pairs and
+    their compare with `target` (32 bytes, little-endian 256-bit) on the device.
+    Returns ([hash32], [hash <= target])."""
+    require_gpu("equihash_pow_check")
+    return native.eh_pow_check_gpu(n, k, [bytes(x) for x in in140s], [bytes(s) for s in solutions], bytes(target),
+                                   device)
+
+
+def equihash_mine(n: int, k: int, prefix108, nonce_first, count: int, target, batch: int = 32, device: int = 0):
+    """Mine `count` nonces of a header to a target on the device: the nonces nonce_first + i
+    (32 bytes or an int; 256-bit little-endian, wrapping) of the header whose 108-byte Equihash
+    input is `prefix108`. Two solvers alternate over the range, each batch pipelined behind the
+    other's (``after=``). Returns every hit [(nonce, solution, block hash)] in nonce order; the
+    host never sees a solution above the target."""
+    require_gpu("equihash_mine")
+    first = nonce_first if isinstance(nonce_first, int) else int.from_bytes(bytes(nonce_first), "little")
+    prefix108, target = bytes(prefix108), bytes(target)
+    solvers = [native.EquihashGpuSolver(n, k, batch, device) for _ in range(2)]
+    hits, pending, prev = [], [], None
+    for i, off in enumerate(range(0, count, batch)):
+        s = solvers[i & 1]
+        if len(pending) == 2:
+            hits += pending.pop(0).collect_pow()["hits"]
+        nonce = ((first + off) % (1 << 256)).to_bytes(32, "little")
+        s.launch_pow(prefix108, nonce, min(batch, count - off), target, after=prev)
+        pending.append(s)
+        prev = s
+    for s in pending:
+        hits += s.collect_pow()["hits"]
+    return hits
+
+
 __all__ = ["sha256d64", "sha256d_batch", "merkle_root", "scan_nonces", "equihash_verify", "ecdsa_verify",
-           "ecdsa_verify_compact", "short_txids", "verify_forkid"]
+           "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine"]
 
 
 def short_txids(k0: int, k1: int, txids, device: int = -1) -> list:

@@ -135,8 +135,6 @@ class DistributedEquihashMiner:
     def mine(self, accept: Callable[[bytes, bytes], bool], max_steps: int = 1000):
         """Run steps until some rank finds (nonce, solution) with accept(...) true.
         All ranks return the same winner (lowest winning rank), or None."""
-        dev = _device()
-        sol_len = self.model.solution_bytes
         for _ in range(max_steps):
             found = None
             for nonce, sols in self.step():
@@ -146,22 +144,83 @@ class DistributedEquihashMiner:
                         break
                 if found:
                     break
-            if self.size == 1 or not dist.is_initialized():
-                if found:
-                    return found
-                continue
-            flag = torch.tensor([self.rank if found else self.size], dtype=torch.int64, device=dev)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            winner = int(flag.item())
-            if winner == self.size:
-                continue
-            payload = torch.zeros(32 + sol_len, dtype=torch.uint8, device=dev)
-            if winner == self.rank:
-                payload.copy_(torch.frombuffer(bytearray(found[0] + found[1]), dtype=torch.uint8).to(dev))
-            dist.broadcast(payload, src=winner)
-            raw = bytes(payload.cpu().tolist())
-            return raw[:32], raw[32:]
+            winner = self._agree(found)
+            if winner:
+                return winner
+        return None
+
+    def _agree(self, found):
+        """One step's winner exchange: every rank gets the (nonce, solution) of the lowest rank
+        that found one (all-reduce MIN over the rank, broadcast from it), or None."""
+        if self.size == 1 or not dist.is_initialized():
+            return found
+        dev = _device()
+        flag = torch.tensor([self.rank if found else self.size], dtype=torch.int64, device=dev)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        winner = int(flag.item())
+        if winner == self.size:
+            return None
+        payload = torch.zeros(32 + self.model.solution_bytes, dtype=torch.uint8, device=dev)
+        if winner == self.rank:
+            payload.copy_(torch.frombuffer(bytearray(found[0] + found[1]), dtype=torch.uint8).to(dev))
+        dist.broadcast(payload, src=winner)
+        raw = bytes(payload.cpu().tolist())
+        return raw[:32], raw[32:]
+
+    def mine_target(self, target: bytes, max_steps: int = 1000):
+        """Run steps until some rank finds a (nonce, solution) whose block hash, SHA256d of
+        header || nonce || compactsize || solution read as a 256-bit little-endian integer, is at
+        or below `target` (32 bytes little-endian). All ranks return the same winner, or None.
+
+        The GPU backend does the whole step on the device (``launch_pow`` / ``collect_pow``: nonce
+        states, solve, encode, hash, compare) and sees only the hits; the CPU backend solves on
+        the CPU and hashes with hashlib."""
+        target = bytes(target)
+        if len(target) != 32:
+            raise ValueError("target must be 32 bytes (little-endian)")
+        if self.solver is not None and len(self.header) != 108:
+            raise ValueError("the device path takes the 108-byte header input")
+        tint = int.from_bytes(target, "little")
+        for _ in range(max_steps):
+            found = None
+            if self.solver is not None:
+                self.solver.launch_pow(self.header, nonce_bytes(self.counter, self.rank), self.batch, target)
+                self.counter += self.batch
+                hits = self.solver.collect_pow()["hits"]
+                if hits:
+                    found = (hits[0][0], hits[0][1])
+            else:
+                for nonce, sols in self.step():
+                    for s in sols:
+                        if int.from_bytes(header_hash(self.header + nonce, s), "little") <= tint:
+                            found = (nonce, s)
+                            break
+                    if found:
+                        break
+            winner = self._agree(found)
+            if winner:
+                return winner
         return None
 
 
-__all__ = ["init_from_env", "world", "shard_bounds", "nonce_bytes", "sharded_verify", "DistributedEquihashMiner"]
+def compact_size(n: int) -> bytes:
+    """Bitcoin's variable-length integer prefix of a vector of n bytes."""
+    if n < 253:
+        return bytes([n])
+    if n <= 0xFFFF:
+        return b"\xfd" + struct.pack("<H", n)
+    if n <= 0xFFFFFFFF:
+        return b"\xfe" + struct.pack("<I", n)
+    return b"\xff" + struct.pack("<Q", n)
+
+
+def header_hash(in140: bytes, solution: bytes) -> bytes:
+    """Block hash of a post-fork header: SHA256d(input || nonce || compactsize || solution)."""
+    import hashlib
+
+    msg = bytes(in140) + compact_size(len(solution)) + bytes(solution)
+    return hashlib.sha256(hashlib.sha256(msg).digest()).digest()
+
+
+__all__ = ["init_from_env", "world", "shard_bounds", "nonce_bytes", "sharded_verify", "DistributedEquihashMiner",
+           "compact_size", "header_hash"]

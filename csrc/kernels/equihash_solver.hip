@@ -47,6 +47,7 @@
 
 #include "crypto/hashes.h"
 #include "kernels/blake2b_device.h"
+#include "kernels/equihash_pow.h"
 #include "kernels/gpu_api.h"
 #include "kernels/hip_util.h"
 
@@ -1404,6 +1405,14 @@ struct EquihashGpuSolver::Impl {
     uint32_t cp_ib = 0, cp_dh = 0, cp_dhm = 0, cp_dx = 0, cp_rmask = 0, cp_imask = 0; // compact parent layout
     std::vector<bool> compact;                  // per stage: compact parent word
     int inflight = 0;
+    // LaunchPow / CollectPow (kernels/equihash_pow.h); the buffers are allocated by the first LaunchPow
+    DevBuf<uint32_t> d_in140, d_powctr, d_win; // inputs of the batch's nonces; winners + repeats counters; winner list
+    HostBuf<uint32_t> h_powctr, h_win;
+    size_t winw = 0;                        // words per winner entry
+    const bcpk::EhPowParams* pow = nullptr; // the job, while LaunchPow enqueues
+    bool pow_inflight = false;              // the launch in flight is a LaunchPow
+    bool pow_collect = false;               // Collect() is running for CollectPow()
+    EhPowJob pow_job;
     int ncu = 1;
     int groups = 1; // nonce groups of a launch (see launch()); 1: the whole batch is generated up front
     bool debug = false, stamp_mode = false;
@@ -1505,9 +1514,25 @@ struct EquihashGpuSolver::Impl {
         (launch_round<C, S + 1>(noff, gn, next), ...);
     }
 
+    template <class C> void alloc_pow() {
+        using P = bcpk::PowCfg<C::N, C::K>;
+        if (d_win.n) return;
+        winw = P::WINW;
+        d_in140.alloc((size_t)batch * 35);
+        d_powctr.alloc(2);
+        h_powctr.alloc(2);
+        d_win.alloc((size_t)batch * C::MAXCAND * P::WINW); // one entry per compact-list entry: no winner is lost
+        h_win.alloc((size_t)batch * C::MAXCAND * P::WINW);
+    }
+
     template <class C> void launch(size_t nstates) {
-        BCP_HIP_CHECK(hipMemcpyAsync(d_states.p, h_states.p, nstates * sizeof(bcpk::EhBaseState),
-                                     hipMemcpyHostToDevice, stream));
+        if (pow) { // the states are built on the device
+            BCP_HIP_CHECK(hipMemsetAsync(d_powctr.p, 0, 2 * sizeof(uint32_t), stream));
+            hipLaunchKernelGGL((bcpk::eh_nonce_states<bcpk::PowCfg<C::N, C::K>>), dim3(((int)nstates + 63) / 64), dim3(64),
+                               0, stream, *pow, (int)nstates, d_in140.p, d_states.p);
+        } else
+            BCP_HIP_CHECK(hipMemcpyAsync(d_states.p, h_states.p, nstates * sizeof(bcpk::EhBaseState),
+                                         hipMemcpyHostToDevice, stream));
         BCP_HIP_CHECK(hipMemsetAsync(d_ncand.p, 0, batch * sizeof(uint32_t), stream));
         BCP_HIP_CHECK(hipMemsetAsync(d_nout.p, 0, sizeof(uint32_t), stream));
         BCP_HIP_CHECK(hipMemsetAsync(d_pdrop.p, 0, d_pdrop.n * sizeof(uint32_t), stream));
@@ -1521,7 +1546,7 @@ struct EquihashGpuSolver::Impl {
         // header-shaped inputs (140 B: g lands at byte 12 of the final block) take the
         // zero-message-word BLAKE2b specialisation
         bool hdr = true;
-        for (size_t i = 0; i < nstates; ++i) {
+        for (size_t i = 0; i < nstates && !pow; ++i) {
             const bcpk::EhBaseState& st = h_states.p[i];
             hdr &= st.g_byte == 12;
             for (int w = 2; w < 16; ++w) hdr &= st.m[w] == 0;
@@ -1569,6 +1594,12 @@ struct EquihashGpuSolver::Impl {
         hipLaunchKernelGGL((bcpk::eh_expand<C>), dim3(C::MAXCAND * nstates), dim3(EB), 0, stream, d_leaf.p, stages,
                            d_ncand.p, d_cand.p, d_idx.p, d_valid.p, d_nout.p, d_out.p);
         BCP_HIP_CHECK(hipEventRecord(ev_rounds, stream));
+        if (pow) {
+            using P = bcpk::PowCfg<C::N, C::K>;
+            const int grid = (int)std::min<size_t>(C::MAXCAND * nstates, 2048); // grid-stride over the entries
+            hipLaunchKernelGGL((bcpk::eh_pow_filter<P>), dim3(grid), dim3(64), 0, stream, *pow, (int)nstates, d_in140.p,
+                               d_nout.p, d_out.p, (uint32_t)(C::MAXCAND * nstates), d_powctr.p, d_win.p, debug ? 1 : 0);
+        }
         BCP_HIP_CHECK(hipGetLastError());
         BCP_HIP_CHECK(hipEventRecord(ev1, stream));
         BCP_HIP_CHECK(
@@ -1582,8 +1613,12 @@ struct EquihashGpuSolver::Impl {
             BCP_HIP_CHECK(hipMemcpyAsync(h_ctr_all.p, d_ctr.p, d_ctr.n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         }
         BCP_HIP_CHECK(hipMemcpyAsync(h_nout.p, d_nout.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        BCP_HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, outq * (C::L + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                     stream));
+        if (pow) { // the winners instead of the index lists
+            BCP_HIP_CHECK(hipMemcpyAsync(h_powctr.p, d_powctr.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            BCP_HIP_CHECK(hipMemcpyAsync(h_win.p, d_win.p, outq * winw * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        } else
+            BCP_HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, outq * (C::L + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                         stream));
         if (debug) // every candidate of nonce 0, valid or not
             BCP_HIP_CHECK(hipMemcpyAsync(h_idx.p, d_idx.p, C::MAXCAND * C::L * sizeof(uint32_t),
                                          hipMemcpyDeviceToHost, stream));
@@ -1783,8 +1818,97 @@ void EquihashGpuSolver::Launch(const std::vector<EhBaseState>& states, const Equ
     impl->after = nullptr;
 }
 
+void EquihashGpuSolver::LaunchPow(const EhPowJob& job) {
+    if (job.count < 1 || job.count > impl->batch) throw std::invalid_argument("LaunchPow: count must be 1..Batch()");
+    if (impl->inflight) throw std::runtime_error("EquihashGpuSolver: Collect() the previous launch first");
+    BCP_HIP_CHECK(hipSetDevice(impl->device));
+    bcpk::EhPowParams p;
+    static_assert(sizeof(p.prefix) == sizeof(job.prefix) && sizeof(p.nonce) == 32 && sizeof(p.target) == 32, "job words");
+    memcpy(p.prefix, job.prefix, sizeof(p.prefix));
+    memcpy(p.nonce, job.nonce_first, 32);
+    memcpy(p.target, job.target_le, 32);
+    impl->pow = &p;
+    try {
+        dispatch_cfg(impl->n, impl->k, [&](auto c) {
+            impl->alloc_pow<decltype(c)>();
+            impl->launch<decltype(c)>((size_t)job.count);
+        });
+    } catch (...) {
+        impl->pow = nullptr;
+        throw;
+    }
+    impl->pow = nullptr;
+    impl->pow_job = job;
+    impl->pow_inflight = true;
+    impl->inflight = job.count;
+}
+
+void EquihashGpuSolver::LaunchPow(const EhPowJob& job, const EquihashGpuSolver& prev) {
+    if (&prev == this) throw std::invalid_argument("EquihashGpuSolver: cannot pipeline behind itself");
+    if (prev.impl->device != impl->device) throw std::invalid_argument("EquihashGpuSolver: pipelined solvers on different devices");
+    impl->after = prev.impl.get();
+    try {
+        LaunchPow(job);
+    } catch (...) {
+        impl->after = nullptr;
+        throw;
+    }
+    impl->after = nullptr;
+}
+
+EhPowResult EquihashGpuSolver::CollectPow() {
+    if (!impl->inflight) throw std::runtime_error("EquihashGpuSolver: nothing in flight");
+    if (!impl->pow_inflight) throw std::runtime_error("EquihashGpuSolver: the launch in flight is a Launch(); use Collect()");
+    const int ns = impl->inflight;
+    impl->pow_collect = true;
+    Collect(); // the wait and the statistics; it decodes no index lists (they stayed on the device)
+    Impl& m = *impl;
+    const size_t nout = m.h_nout.p[0], nwin = m.h_powctr.p[0], ndup = m.h_powctr.p[1];
+    if (nwin > m.outq) // more winners than the per-batch copy holds: fetch the rest
+        BCP_HIP_CHECK(hipMemcpy(m.h_win.p + m.outq * m.winw, m.d_win.p + m.outq * m.winw,
+                                (nwin - m.outq) * m.winw * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    EhPowResult res;
+    res.solutions = nout - ndup;
+    m.stats.solutions += res.solutions;
+    const size_t solw = (m.winw - 11) * 4;
+    // the list is in completion order: by position in the nonce range, then by hash as an integer
+    std::vector<const uint32_t*> ents;
+    for (size_t e = 0; e < nwin; ++e) {
+        const uint32_t* p = m.h_win.p + e * m.winw;
+        if (p[0] < (uint32_t)ns) ents.push_back(p);
+    }
+    std::sort(ents.begin(), ents.end(), [](const uint32_t* a, const uint32_t* b) {
+        if (a[0] != b[0]) return a[0] < b[0];
+        for (int i = 7; i >= 0; --i)
+            if (a[3 + i] != b[3 + i]) return a[3 + i] < b[3 + i];
+        return a[1] < b[1];
+    });
+    for (const uint32_t* p : ents) {
+        EhPowHit h;
+        uint64_t carry = p[0];
+        for (int q = 0; q < 4; ++q) { // nonce_first + position, 256-bit little-endian
+            uint64_t a;
+            memcpy(&a, m.pow_job.nonce_first + 8 * q, 8);
+            const uint64_t s = a + carry;
+            carry = s < a ? 1 : 0;
+            memcpy(h.nonce + 8 * q, &s, 8);
+        }
+        memcpy(h.hash, p + 3, 32);
+        h.solution.assign(reinterpret_cast<const unsigned char*>(p + 11), reinterpret_cast<const unsigned char*>(p + 11) + solw);
+        if (m.debug) {
+            res.all.push_back(h);
+            res.all_pass.push_back(p[2] ? 1 : 0);
+        }
+        if (p[2]) res.hits.push_back(std::move(h));
+    }
+    return res;
+}
+
 std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Collect() {
     if (!impl->inflight) throw std::runtime_error("EquihashGpuSolver: nothing in flight");
+    const bool pow = impl->pow_collect; // called by CollectPow: the wait and the statistics only
+    if (impl->pow_inflight && !pow) throw std::runtime_error("EquihashGpuSolver: the launch in flight is a LaunchPow(); use CollectPow()");
+    impl->pow_collect = impl->pow_inflight = false;
     BCP_HIP_CHECK(hipSetDevice(impl->device));
     BCP_HIP_CHECK(hipStreamSynchronize(impl->stream));
     const int ns = impl->inflight;
@@ -1851,7 +1975,7 @@ std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Collect() {
     std::vector<std::vector<std::vector<uint32_t>>> out(ns);
     const size_t ew = impl->L + 2; // compact-list entry: nonce, candidate, L indices
     const size_t nout = impl->h_nout.p[0];
-    if (nout > impl->outq) // more valid solutions than the per-batch copy holds: fetch the rest
+    if (!pow && nout > impl->outq) // more valid solutions than the per-batch copy holds: fetch the rest
         BCP_HIP_CHECK(hipMemcpy(impl->h_out.p + impl->outq * ew, impl->d_out.p + impl->outq * ew,
                                 (nout - impl->outq) * ew * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (impl->debug) {
@@ -1874,7 +1998,7 @@ std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Collect() {
     // the list is in completion order: put every nonce's solutions in candidate order
     std::vector<std::pair<uint64_t, const uint32_t*>> ents;
     ents.reserve(nout);
-    for (size_t e = 0; e < nout; ++e) {
+    for (size_t e = 0; e < nout && !pow; ++e) {
         const uint32_t* p = impl->h_out.p + e * ew;
         if (p[0] < (uint32_t)ns) ents.emplace_back(((uint64_t)p[0] << 32) | p[1], p + 2);
     }

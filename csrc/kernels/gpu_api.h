@@ -57,6 +57,29 @@ struct EhGpuStats {
     std::vector<std::vector<uint32_t>> debug_cands;                  // debug: every candidate of nonce 0 (valid or not)
 };
 
+// "Mine this header to this target" on the device (csrc/kernels/equihash_pow.h): the nonces
+// nonce_first + i, i < count (256-bit little-endian, wrapping), of the header whose
+// CEquihashInput is `prefix`; a solution wins when SHA256d(header), read as a 256-bit
+// little-endian integer, is at or below the target.
+struct EhPowJob {
+    unsigned char prefix[108];
+    unsigned char nonce_first[32];
+    int count;
+    unsigned char target_le[32];
+};
+struct EhPowHit {
+    unsigned char nonce[32];
+    std::vector<unsigned char> solution; // minimal encoding
+    unsigned char hash[32];              // the block hash (SHA256d of the whole header)
+};
+struct EhPowResult {
+    std::vector<EhPowHit> hits; // sorted by position in the nonce range, then by hash (as an integer)
+    uint64_t solutions = 0;     // all valid solutions of the batch, winners or not
+    // debug mode only: every valid solution in the same order, and whether it met the target
+    std::vector<EhPowHit> all;
+    std::vector<uint8_t> all_pass;
+};
+
 // Batched Equihash solver: one launch sequence solves `batch` nonces at once
 // (8 + 3 kernels per batch, bucket-per-workgroup collision rounds in LDS).
 class EquihashGpuSolver {
@@ -79,6 +102,15 @@ public:
     // generation.
     void Launch(const std::vector<EhBaseState>& states, const EquihashGpuSolver& prev);
     std::vector<std::vector<std::vector<uint32_t>>> Collect();
+    // The mining step without the host: the nonce states are built on the device, the unchanged
+    // solve sequence runs, and a filter kernel encodes every valid solution, hashes its header
+    // and keeps the ones at or below the target; only those are copied back. job.count <=
+    // Batch(). The second form is pipelined like Launch(states, prev). CollectPow updates the
+    // statistics as Collect does. A LaunchPow is collected with CollectPow and a Launch with
+    // Collect; the other pairing throws.
+    void LaunchPow(const EhPowJob& job);
+    void LaunchPow(const EhPowJob& job, const EquihashGpuSolver& prev);
+    EhPowResult CollectPow();
     const EhGpuStats& Stats() const;
     void SetDebug(bool on);   // collect per-stage bucket statistics (extra D2H copies)
     void SetStampMode(bool on); // diagnostic: launch phase-timestamped round kernels
@@ -102,6 +134,14 @@ private:
 std::vector<uint8_t> EquihashVerifyBatch(unsigned n, unsigned k, const std::vector<EhBaseState>& states,
                                          const std::vector<std::vector<unsigned char>>& solutions,
                                          int device = -1);
+
+// Block hashes of cnt headers given as (140-byte Equihash input, minimal solution) pairs:
+// hashes[32*i ..] = SHA256d(in140_i || compactsize || sol_i), pass[i] = 1 iff that hash, as a
+// 256-bit little-endian integer, is at or below the target. One workgroup per pair, the device
+// functions of the miner's filter kernel.
+void EquihashPowCheckBatch(unsigned n, unsigned k, const unsigned char* in140, const unsigned char* sols, size_t cnt,
+                           const unsigned char target_le[32], std::vector<unsigned char>& hashes,
+                           std::vector<uint8_t>& pass, int device = -1);
 
 // --------------------------------------------------------------- SHA-256d
 // out[i] = SHA256d(in[offs[i] .. offs[i]+lens[i]))

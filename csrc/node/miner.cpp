@@ -397,6 +397,87 @@ EhSearchResult EquihashSearchGpu(unsigned n, unsigned k, const std::vector<unsig
     return res;
 }
 
+EhSearchResult EquihashSearchGpu(unsigned n, unsigned k, const std::vector<unsigned char>& equihashInput,
+                                 const uint256& nonce0, uint64_t maxNonces, const uint256& target,
+                                 std::vector<int> devices, const std::atomic<bool>* cancel) {
+    if (devices.empty()) devices = GetMinerGpuDevices();
+    if (devices.empty()) throw std::runtime_error("EquihashSearchGpu: no GPU device");
+    gpu::EhPowJob job0;
+    if (equihashInput.size() != sizeof(job0.prefix))
+        throw std::invalid_argument("EquihashSearchGpu: the device path takes the 108-byte header input");
+    memcpy(job0.prefix, equihashInput.data(), sizeof(job0.prefix));
+    memcpy(job0.target_le, target.begin(), 32);
+    const arith_uint256 n0 = UintToArith256(nonce0);
+    std::atomic<uint64_t> next{0}, nNonces{0}, nSols{0}, nHits{0};
+    std::atomic<bool> stop{false};
+    std::mutex resMutex;
+    EhSearchResult res;
+    uint64_t bestPos = 0; // position in the range of the hit held in res
+    std::string firstError;
+    auto worker = [&](int device) {
+        try {
+            DeviceMiner& dm = GetDeviceMiner(device, n, k);
+            std::lock_guard<std::mutex> busy(dm.busy);
+            const int B = dm.s[0]->Batch();
+            uint64_t pendStart[2] = {0, 0};
+            int pendCount[2] = {0, 0};
+            auto launch = [&](int slot) -> bool {
+                if (stop.load() || (cancel && cancel->load())) return false;
+                const uint64_t start = next.fetch_add((uint64_t)B);
+                if (start >= maxNonces) return false;
+                gpu::EhPowJob job = job0;
+                job.count = (int)std::min<uint64_t>((uint64_t)B, maxNonces - start);
+                const uint256 first = ArithToUint256(n0 + arith_uint256(start + 1));
+                memcpy(job.nonce_first, first.begin(), 32);
+                pendStart[slot] = start;
+                pendCount[slot] = job.count;
+                dm.s[slot]->LaunchPow(job);
+                return true;
+            };
+            auto collect = [&](int slot) {
+                const gpu::EhPowResult r = dm.s[slot]->CollectPow();
+                nNonces += (uint64_t)pendCount[slot];
+                nSols += r.solutions;
+                nHits += r.hits.size();
+                if (r.hits.empty()) return;
+                // hits are sorted by position: the first is the batch's lowest nonce
+                const gpu::EhPowHit& h = r.hits.front();
+                uint256 nonce;
+                memcpy(nonce.begin(), h.nonce, 32);
+                const uint64_t pos = (UintToArith256(nonce) - n0).GetLow64(); // 1..maxNonces
+                std::lock_guard<std::mutex> l(resMutex);
+                if (!res.found || pos < bestPos) {
+                    res.found = true;
+                    bestPos = pos;
+                    res.nonce = nonce;
+                    res.solution = h.solution;
+                    memcpy(res.hash.begin(), h.hash, 32);
+                }
+                stop = true;
+            };
+            bool inflight[2] = {launch(0), false};
+            for (int cur = 0;; cur ^= 1) { // launch the next batch, then collect the running one
+                inflight[cur ^ 1] = launch(cur ^ 1);
+                if (inflight[cur]) collect(cur);
+                inflight[cur] = false;
+                if (!inflight[cur ^ 1]) break;
+            }
+        } catch (const std::exception& e) {
+            std::lock_guard<std::mutex> l(resMutex);
+            if (firstError.empty()) firstError = e.what();
+            stop = true;
+        }
+    };
+    std::vector<std::thread> threads;
+    for (int d : devices) threads.emplace_back(worker, d);
+    for (auto& t : threads) t.join();
+    res.nonces = nNonces.load();
+    res.solutions = nSols.load();
+    res.hits = nHits.load();
+    if (!res.found && !firstError.empty()) throw std::runtime_error("EquihashSearchGpu: " + firstError);
+    return res;
+}
+
 static bool SolveLegacy(CBlock& block, const Consensus::Params& cp, uint64_t& nMaxTries, bool useGpu,
                         const std::atomic<bool>* cancel) {
     // nonce lives in the low 32 bits of nNonce in the 80-byte legacy header
@@ -471,6 +552,48 @@ static bool SolveEquihash(CBlock& block, const CChainParams& params, uint64_t& n
         return CheckProofOfWork(block.GetHash(cp), block.nBits, true, cp);
     };
     const bool gpuOk = useGpu && gpu::GpuAvailable(); // (48,5) too: 0.086 vs 0.109 ms per nonce batch, profiles/baseline_metrics_r2s4.md
+    // The whole step on the device: only solutions whose block hash meets the target come back
+    // (csrc/kernels/equihash_pow.h). The target is range-checked as CheckProofOfWork does, and
+    // the chosen hit is checked again on the CPU before it is used.
+    bool fNegative = false, fOverflow = false;
+    arith_uint256 bnTarget;
+    bnTarget.SetCompact(block.nBits, &fNegative, &fOverflow);
+    const bool targetOk = !fNegative && bnTarget != 0 && !fOverflow && bnTarget <= UintToArith256(cp.PowLimit(true));
+    bool devicePath = gpuOk && targetOk && input.size() == 108;
+    while (devicePath && nMaxTries > 0) {
+        EhSearchResult r;
+        const int64_t t0 = GetTimeMicros();
+        try {
+            r = EquihashSearchGpu(ep.N, ep.K, input, block.nNonce, nMaxTries, ArithToUint256(bnTarget), {}, cancel);
+        } catch (const std::exception& e) {
+            LogPrintf("SolveEquihash: device target filter failed (%s); using the host check\n", e.what());
+            devicePath = false;
+            break;
+        }
+        {
+            std::lock_guard<std::mutex> ls(g_minerMutex);
+            g_minerStats.gpu_ms += (GetTimeMicros() - t0) / 1000.0;
+            g_minerStats.eh_nonces += r.nonces;
+            g_minerStats.eh_solutions += r.solutions;
+            g_minerStats.eh_pow_hits += r.hits;
+        }
+        if (r.found) {
+            // the nonces up to the hit are used up, whether it survives the recheck or not
+            const uint64_t used = (UintToArith256(r.nonce) - UintToArith256(block.nNonce)).GetLow64();
+            nMaxTries -= std::min(nMaxTries, used);
+            block.nNonce = r.nonce;
+            if (tryState(r.solution)) return true;
+            block.nSolution.clear();
+            LogPrintf("SolveEquihash: GPU hit at nonce %s failed the CPU proof-of-work recheck; searching on\n",
+                      r.nonce.GetHex().c_str());
+            if (cancel && cancel->load()) return false;
+            continue;
+        }
+        nMaxTries -= std::min(nMaxTries, r.nonces);
+        block.nNonce = ArithToUint256(UintToArith256(block.nNonce) + arith_uint256(r.nonces));
+        return false;
+    }
+    if (gpuOk && (devicePath || nMaxTries == 0)) return false; // the device path used up the tries
     if (gpuOk) {
         const CBlockHeader hdr = block.GetBlockHeader();
         auto accept = [&](const uint256& nonce, const std::vector<unsigned char>& soln) {

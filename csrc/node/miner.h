@@ -75,6 +75,7 @@ std::string GetSubVersionEB(uint64_t maxBlockSize); // "8.0" for 8 MB
 // nMaxTries counts nonces (legacy) or Equihash instances (post-fork).
 struct MinerStats {
     uint64_t sha_nonces = 0, eh_nonces = 0, eh_solutions = 0, blocks = 0;
+    uint64_t eh_pow_hits = 0; // Equihash solutions the device filter found at or below the target
     double gpu_ms = 0;
 };
 bool SolveBlock(CBlock& block, const CChainParams& params, uint64_t& nMaxTries, bool useGpu,
@@ -91,10 +92,20 @@ struct EhSearchResult {
     uint256 nonce;                        // nonce of the accepted solution
     std::vector<unsigned char> solution;  // minimal encoding
     uint64_t nonces = 0, solutions = 0;   // instances solved / solutions seen (all devices)
+    uint256 hash;                         // target overload: the block hash of the chosen hit
+    uint64_t hits = 0;                    // target overload: solutions at or below the target
 };
 EhSearchResult EquihashSearchGpu(unsigned n, unsigned k, const std::vector<unsigned char>& equihashInput,
                                  const uint256& nonce0, uint64_t maxNonces,
                                  const std::function<bool(const uint256&, const std::vector<unsigned char>&)>& accept,
+                                 std::vector<int> devices = {}, const std::atomic<bool>* cancel = nullptr);
+// The same search with the rest of the mining step on the device (EquihashGpuSolver::LaunchPow):
+// the nonce states are built there, and every solution is encoded, its header hashed and the hash
+// compared with `target` (256-bit little-endian) by the filter kernel, so the host sees only the
+// solutions that meet the target. equihashInput is the 108-byte CEquihashInput. The first batch
+// with a hit ends the search; of the hits collected the one with the lowest nonce is returned.
+EhSearchResult EquihashSearchGpu(unsigned n, unsigned k, const std::vector<unsigned char>& equihashInput,
+                                 const uint256& nonce0, uint64_t maxNonces, const uint256& target,
                                  std::vector<int> devices = {}, const std::atomic<bool>* cancel = nullptr);
 // -gpudevices: devices used by the miner (empty: every visible device).
 void SetMinerGpuDevices(const std::vector<int>& devices);

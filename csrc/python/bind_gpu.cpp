@@ -71,6 +71,45 @@ void bind_gpu(pyb::module_& m) {
                  }
                  return out;
              })
+        // The mining step on the device: nonces nonce_first .. nonce_first + count - 1 of the header
+        // with this 108-byte input; collect_pow returns only the solutions whose block hash is at
+        // or below the target (both 32-byte little-endian).
+        .def(
+            "launch_pow",
+            [](gpu::EquihashGpuSolver& s, const pyb::bytes& prefix108, const pyb::bytes& nonce_first32, int count,
+               const pyb::bytes& target32, const gpu::EquihashGpuSolver* after) {
+                const auto p = to_vec(prefix108), n0 = to_vec(nonce_first32), t = to_vec(target32);
+                gpu::EhPowJob job;
+                if (p.size() != sizeof(job.prefix) || n0.size() != 32 || t.size() != 32)
+                    throw std::invalid_argument("launch_pow: prefix is 108 bytes, nonce_first and target are 32");
+                memcpy(job.prefix, p.data(), sizeof(job.prefix));
+                memcpy(job.nonce_first, n0.data(), 32);
+                memcpy(job.target_le, t.data(), 32);
+                job.count = count;
+                if (after) s.LaunchPow(job, *after);
+                else s.LaunchPow(job);
+            },
+            pyb::arg("prefix108"), pyb::arg("nonce_first32"), pyb::arg("count"), pyb::arg("target32"),
+            pyb::arg("after") = nullptr)
+        .def("collect_pow",
+             [](gpu::EquihashGpuSolver& s) {
+                 gpu::EhPowResult r;
+                 {
+                     pyb::gil_scoped_release rel;
+                     r = s.CollectPow();
+                 }
+                 pyb::list hits, all;
+                 for (const auto& h : r.hits)
+                     hits.append(pyb::make_tuple(to_bytes(h.nonce, 32), to_bytes(h.solution), to_bytes(h.hash, 32)));
+                 for (size_t i = 0; i < r.all.size(); ++i)
+                     all.append(pyb::make_tuple(to_bytes(r.all[i].nonce, 32), to_bytes(r.all[i].solution),
+                                                to_bytes(r.all[i].hash, 32), (bool)r.all_pass[i]));
+                 pyb::dict d;
+                 d["hits"] = hits;
+                 d["solutions"] = r.solutions;
+                 d["all"] = all;
+                 return d;
+             })
         // Launch+collect many batches back to back; returns total solutions (for benchmarking).
         .def("run_nonces",
              [](gpu::EquihashGpuSolver& s, const std::vector<CBlake2b>& sts) {
@@ -146,6 +185,64 @@ void bind_gpu(pyb::module_& m) {
         },
         pyb::arg("n"), pyb::arg("k"), pyb::arg("input"), pyb::arg("nonce0"), pyb::arg("max_nonces"),
         pyb::arg("devices") = std::vector<int>{});
+
+    // The same search with the target filter on the device (the EquihashSearchGpu overload that
+    // takes the target): input is the 108-byte header input, target 32 bytes little-endian.
+    m.def(
+        "eh_search_gpu_target",
+        [](unsigned n, unsigned k, const pyb::bytes& input, const pyb::bytes& nonce0, uint64_t maxNonces,
+           const pyb::bytes& target, const std::vector<int>& devices) {
+            const auto in = to_vec(input), n0 = to_vec(nonce0), tg = to_vec(target);
+            if (n0.size() != 32 || tg.size() != 32) throw std::invalid_argument("nonce0 and target must be 32 bytes");
+            uint256 start, t;
+            memcpy(start.begin(), n0.data(), 32);
+            memcpy(t.begin(), tg.data(), 32);
+            EhSearchResult r;
+            {
+                pyb::gil_scoped_release rel;
+                r = EquihashSearchGpu(n, k, in, start, maxNonces, t, devices);
+            }
+            pyb::dict d;
+            d["found"] = r.found;
+            d["nonce"] = to_bytes(r.nonce.begin(), 32);
+            d["solution"] = to_bytes(r.solution.data(), r.solution.size());
+            d["hash"] = to_bytes(r.hash.begin(), 32);
+            d["nonces"] = r.nonces;
+            d["solutions"] = r.solutions;
+            d["hits"] = r.hits;
+            return d;
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("input"), pyb::arg("nonce0"), pyb::arg("max_nonces"), pyb::arg("target"),
+        pyb::arg("devices") = std::vector<int>{});
+
+    // Block hashes and target compare of (140-byte input, solution) pairs on the device:
+    // returns ([hash32], [passed]).
+    m.def(
+        "eh_pow_check_gpu",
+        [](unsigned n, unsigned k, const std::vector<pyb::bytes>& in140s, const std::vector<pyb::bytes>& sols,
+           const pyb::bytes& target32, int device) {
+            const size_t sw = gpu::EquihashSolutionBytes(n, k);
+            const auto t = to_vec(target32);
+            if (in140s.size() != sols.size() || t.size() != 32)
+                throw std::invalid_argument("eh_pow_check_gpu: one solution per input, 32-byte target");
+            std::vector<unsigned char> in, so, hashes;
+            for (size_t i = 0; i < sols.size(); ++i) {
+                const auto a = to_vec(in140s[i]), b = to_vec(sols[i]);
+                if (a.size() != 140 || b.size() != sw) throw std::invalid_argument("eh_pow_check_gpu: input or solution length");
+                in.insert(in.end(), a.begin(), a.end());
+                so.insert(so.end(), b.begin(), b.end());
+            }
+            std::vector<uint8_t> pass;
+            {
+                pyb::gil_scoped_release rel;
+                gpu::EquihashPowCheckBatch(n, k, in.data(), so.data(), sols.size(), t.data(), hashes, pass, device);
+            }
+            pyb::list hl;
+            for (size_t i = 0; i < sols.size(); ++i) hl.append(to_bytes(hashes.data() + 32 * i, 32));
+            return pyb::make_tuple(hl, std::vector<bool>(pass.begin(), pass.end()));
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("in140s"), pyb::arg("solutions"), pyb::arg("target32"),
+        pyb::arg("device") = -1);
 
     m.def(
         "eh_verify_batch_gpu",

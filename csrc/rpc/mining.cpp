@@ -111,6 +111,7 @@ static UniValue getmininginfo(const JSONRPCRequest& req) {
     gpu.pushKV("enabled", n.useGpu);
     gpu.pushKV("equihash_nonces", (uint64_t)ms.eh_nonces);
     gpu.pushKV("equihash_solutions", (uint64_t)ms.eh_solutions);
+    gpu.pushKV("equihash_pow_hits", (uint64_t)ms.eh_pow_hits);
     gpu.pushKV("sha256d_nonces", (uint64_t)ms.sha_nonces);
     gpu.pushKV("gpu_ms", ms.gpu_ms);
     obj.pushKV("miner", gpu);

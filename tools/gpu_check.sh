@@ -11,6 +11,8 @@
 #   eh-ab TAG [REPS]     solver builds under ab/*/: GPU equihash tests + (200,9)/(96,5) CPU
 #                        cross-checks of the in-tree build, serial batch timing per build,
 #                        interleaved headline A/B (tools/ab_bench.py, REPS >= 20 recommended)
+#   eh-pow TAG [REPS]    device target filter: its GPU tests, the launch_pow / collect_pow loop next to
+#                        launch / collect (tools/eh_pow_loop.py, alternated), a kernel trace of the pow loop
 #   eh-trace TAG         per-kernel durations of each ab/ build (serial solver) and the
 #                        two-solver timeline of the bench (tools/eh_timeline.py)
 #   eh-phases TAG        per-phase cycle stamps of the round kernels for each ab/ build
@@ -92,6 +94,14 @@ eh-ab)
   done
   timeout -k 10 900 python -u tools/ab_bench.py --reps "${3:-20}" ab/*/$EXT > "$O/ab.log" 2>&1
   tail -n 3 "$O/ab.log" ;;
+eh-pow)
+  timeout -k 10 300 python -u -m pytest tests/test_equihash_pow.py -x -q -m gpu > "$O/t.log" 2>&1 || { tail -n 30 "$O/t.log"; exit 1; }
+  tail -n 1 "$O/t.log"
+  timeout -k 10 400 python -u tools/eh_pow_loop.py --reps "${3:-5}" > "$O/powloop.log" 2>&1
+  tail -n 1 "$O/powloop.log"
+  (cd /tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o k -- \
+    python3 "$R/tools/eh_pow_loop.py" --once pow --steps 6 > "$O/prof.log" 2>&1)
+  python3 tools/prof_summary.py "$O/prof/k_kernel_trace.csv" | grep -E 'kernel|eh_nonce_states|eh_pow_filter|total' ;;
 eh-trace)
   for b in $(builds); do
     (cd /tmp && BCP_NATIVE_PATH=$R/ab/$b/$EXT timeout -k 10 120 rocprofv3 --kernel-trace --stats -d "$O/$b" -o k -- \
