@@ -158,17 +158,70 @@ def verify(pub: bytes, r: int, s: int, msg32: bytes, require_low_s=True) -> bool
     return X is not None and X[0] % N == r
 
 
-def recover(r: int, s: int, recid: int, msg32: bytes):
-    x = r + (N if recid & 2 else 0)
-    if x >= P:
+def lift_x(x: int, odd):
+    """The curve point with this x and the given parity of y, or None when x >= p or x is not
+    the abscissa of a point."""
+    if not 0 <= x < P:
         return None
     y2 = (pow(x, 3, P) + 7) % P
     y = pow(y2, (P + 1) // 4, P)
     if y * y % P != y2:
         return None
-    if (y & 1) != (recid & 1):
+    if (y & 1) != (1 if odd else 0):
         y = P - y
-    R = (x, y)
+    return (x, y)
+
+
+def recover_with(R, r: int, s: int, msg32: bytes):
+    """The key Q = (s*R - z*G) / r: with it the verifier's u1*G + u2*Q is exactly R, whatever r
+    is. (r, s) is then a valid signature iff r = x(R) mod n."""
     z = int.from_bytes(msg32, "big") % N
     rinv = pow(r, -1, N)
     return point_add(point_mul(s * rinv % N, R), point_mul((-z * rinv) % N))
+
+
+def recover(r: int, s: int, recid: int, msg32: bytes):
+    R = lift_x(r + (N if recid & 2 else 0), recid & 1)
+    if R is None:
+        return None
+    return recover_with(R, r, s, msg32)
+
+
+# GLV endomorphism: LAMBDA^3 = 1 (mod n), BETA^3 = 1 (mod p), LAMBDA * (x, y) = (BETA * x, y)
+LAMBDA = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
+BETA = 0x7AE96A2B657C07106E64479EAC3434E99CF0497512F58995C1396C28719501EE
+
+
+def forge(u1: int, u2: int, Q, r: int | None = None):
+    """(r, s, msg32) for which a verifier computes exactly these u1 = z/s and u2 = r/s under the
+    key Q (any curve point; no secret key is needed): R = u1*G + u2*Q, r = x(R) mod n, s = r/u2,
+    z = u1*s. The signature is valid by construction. When R is the point at infinity there is no
+    valid r: the caller passes one, and the signature is invalid for every such r. s may come out
+    above n/2; a verifier that normalises s then works with (-u1, -u2)."""
+    u1 %= N
+    u2 %= N
+    if u2 == 0:
+        raise ValueError("u2 = 0 would need r = 0")
+    R = point_add(point_mul(u1), point_mul(u2, Q))
+    if R is None:
+        if r is None:
+            raise ValueError("u1*G + u2*Q is the point at infinity: give r")
+    else:
+        if r is not None:
+            raise ValueError("r is determined by R")
+        r = R[0] % N
+    if not 0 < r < N:
+        raise ValueError("r out of range")
+    s = r * pow(u2, -1, N) % N
+    return r, s, (u1 * s % N).to_bytes(32, "big")
+
+
+def sign_with(k: int, d: int, s: int):
+    """(r, s, msg32) valid under the key d*G with the nonce k and this very s: r = x(k*G) mod n,
+    z = s*k - r*d."""
+    if not (0 < k < N and 0 < d < N and 0 < s < N):
+        raise ValueError("k, d, s must be in [1, n-1]")
+    r = point_mul(k)[0] % N
+    if r == 0:
+        raise ValueError("r = 0")
+    return r, s, ((s * k - r * d) % N).to_bytes(32, "big")
