@@ -6,7 +6,7 @@ an explicit ``use_gpu=False``.
 
 Two input paths:
 * **Device-resident** (``torch.uint8`` tensors on the GPU): ``sha256d64``,
-  ``short_txids`` and ``ecdsa_verify_compact`` hand the tensors' device pointers to
+  ``short_txids``, ``ecdsa_verify_compact`` and ``check_headers`` hand the tensors' device pointers to
   the kernels and enqueue them on the tensors' current torch stream
   (``torch.cuda.current_stream().cuda_stream``).  Results come back as GPU tensors;
   nothing is copied to the host and nothing synchronises, so the ops compose with
@@ -22,6 +22,8 @@ Kernel map (reference hot loops):
   scan_nonces        K5  legacy SHA-256d header nonce scan           sha256.hip
   equihash_verify    K4  batched IsValidSolution                     equihash_verify.hip
   equihash_pow_check K5  block hash + target compare of headers      equihash_pow.hip
+  check_headers      K4/K5 whole CheckBlockHeader of a header batch: solution, hash, nBits, links
+                                                                     equihash_verify.hip + equihash_header.h
   equihash_mine      K1-K5 nonce states, solve, encode, hash, filter  equihash_solver.hip + equihash_pow.h
   ecdsa_verify       K8  batched secp256k1 verify                    secp256k1.hip
   verify_forkid      K8  block-path deferred checks -> verify batch  secp256k1.hip (GpuVerifyDeferred)
@@ -129,6 +131,64 @@ def equihash_pow_check(n: int, k: int, in140s, solutions, target, device: int = 
                                    device)
 
 
+# status bits of check_headers (gpu::HeaderStatus, csrc/kernels/gpu_api.h)
+HDR_SOLUTION_VALID, HDR_TARGET_LEGAL, HDR_HASH_MEETS, HDR_HASH_VALID, HDR_LINKED = 1, 2, 4, 8, 16
+
+
+def check_headers(n: int, k: int, in140s, solutions, pow_limit, lenok=None, use_gpu: bool = True, device: int = -1,
+                  out=None):
+    """The whole of CheckBlockHeader for a batch of post-fork headers in one device pass: Equihash
+    solution, block hash, nBits decode (SetCompact), target against `pow_limit` (32 bytes,
+    little-endian 256-bit), hash <= target, and whether each header names the one before it.
+
+    Host path: `in140s` is a list of 140-byte Equihash inputs and `solutions` a list of minimal
+    solutions (one of another length gets HDR_HASH_VALID clear); returns ([status], [hash32]).
+    ``use_gpu=False`` computes the same with the CPU consensus code.
+
+    Device-resident path: `in140s` [cnt,140] and `solutions` [cnt, solution bytes] are
+    ``torch.uint8`` GPU tensors, `lenok` an optional [cnt] uint8 tensor (0: the header's solution
+    had another length); the kernels are enqueued on the current torch stream and the result is
+    (status [cnt] uint8, hashes [cnt,32] uint8) on the GPU. `out` = (status, hashes) tensors of
+    at least that size are written in place instead (only their first cnt rows)."""
+    pow_limit = bytes(pow_limit)
+    if _on_gpu(in140s):
+        require_gpu("check_headers")
+        if not use_gpu:
+            raise ValueError("check_headers: GPU tensors with use_gpu=False")
+        sw = (1 << k) * (n // (k + 1) + 1) // 8  # bytes of a minimal solution
+        x, s_ = _u8(in140s, "in140s").view(-1), _u8(solutions, "solutions").view(-1)
+        cnt = x.numel() // 140
+        if x.numel() != cnt * 140 or s_.numel() != cnt * sw:
+            raise ValueError("check_headers: in140s is [cnt,140], solutions [cnt,%d]" % sw)
+        ok = torch.ones(cnt, dtype=torch.uint8, device=x.device) if lenok is None else _u8(lenok, "lenok").view(-1)
+        if ok.numel() != cnt or not (x.device == s_.device == ok.device):
+            raise ValueError("check_headers: lenok is [cnt]; all inputs on one device")
+        if x.data_ptr() % 4:
+            x = x.clone()  # the kernels read 32-bit words
+        if s_.data_ptr() % 4:
+            s_ = s_.clone()
+        if out is None:
+            status = torch.empty(cnt, dtype=torch.uint8, device=x.device)
+            hashes = torch.empty((cnt, 32), dtype=torch.uint8, device=x.device)
+        else:
+            status, hashes = out
+            if not (_on_gpu(status) and _on_gpu(hashes) and status.dtype == hashes.dtype == torch.uint8 and
+                    status.is_contiguous() and hashes.is_contiguous() and status.device == hashes.device == x.device):
+                raise ValueError("check_headers: out is (status, hashes), contiguous uint8 tensors on the inputs' device")
+            if status.numel() < cnt or hashes.numel() < 32 * cnt or hashes.data_ptr() % 4:
+                raise ValueError("check_headers: out tensors too small or hashes not 4-byte aligned")
+        scratch = torch.empty(max(cnt, 1) * native.eh_check_headers_scratch_bytes(1), dtype=torch.uint8, device=x.device)
+        dev, stream = _dev_stream(x)
+        native.eh_check_headers_device(n, k, x.data_ptr(), s_.data_ptr(), ok.data_ptr(), pow_limit, scratch.data_ptr(),
+                                       status.data_ptr(), hashes.data_ptr(), cnt, dev, stream)
+        return status, hashes
+    ins, sols = [bytes(a) for a in in140s], [bytes(s) for s in solutions]
+    if not use_gpu:
+        return native.eh_check_headers_cpu(n, k, ins, sols, pow_limit)
+    require_gpu("check_headers")
+    return native.eh_check_headers_gpu(n, k, ins, sols, pow_limit, device)
+
+
 def equihash_mine(n: int, k: int, prefix108, nonce_first, count: int, target, batch: int = 32, device: int = 0):
     """Mine `count` nonces of a header to a target on the device: the nonces nonce_first + i
     (32 bytes or an int; 256-bit little-endian, wrapping) of the header whose 108-byte Equihash
@@ -154,7 +214,7 @@ def equihash_mine(n: int, k: int, prefix108, nonce_first, count: int, target, ba
 
 
 __all__ = ["sha256d64", "sha256d_batch", "merkle_root", "scan_nonces", "equihash_verify", "ecdsa_verify",
-           "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine"]
+           "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine", "check_headers"]
 
 
 def short_txids(k0: int, k1: int, txids, device: int = -1) -> list:

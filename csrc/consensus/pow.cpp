@@ -62,12 +62,16 @@ uint32_t CalculateNextWorkRequired(const CBlockIndex* pindexPrev, int64_t nFirst
     return bnNew.GetCompact();
 }
 
-bool CheckProofOfWork(const uint256& hash, uint32_t nBits, bool postfork, const Consensus::Params& params) {
+bool CheckProofOfWork(const uint256& hash, uint32_t nBits, const arith_uint256& powLimit) {
     bool fNegative, fOverflow;
     arith_uint256 bnTarget;
     bnTarget.SetCompact(nBits, &fNegative, &fOverflow);
-    if (fNegative || bnTarget == 0 || fOverflow || bnTarget > UintToArith256(params.PowLimit(postfork))) return false;
+    if (fNegative || bnTarget == 0 || fOverflow || bnTarget > powLimit) return false;
     return UintToArith256(hash) <= bnTarget;
+}
+
+bool CheckProofOfWork(const uint256& hash, uint32_t nBits, bool postfork, const Consensus::Params& params) {
+    return CheckProofOfWork(hash, nBits, UintToArith256(params.PowLimit(postfork)));
 }
 
 // Work done between two blocks scaled to the target spacing, bounded to [72, 288] spacings.
@@ -137,12 +141,84 @@ bool CheckEquihashSolution(const CBlockHeader* pblock, const CChainParams& param
     return EhIsValidSolution(ep, EquihashStateFor(pblock, ep), pblock->nSolution);
 }
 
+// consecutive failures of the header batches' GPU path (both batch functions below)
+static std::atomic<int> gpuFailures{0};
+
+// headers [lo, hi) into a lane's pinned staging (gpu::VerifyLane::EquihashHeaders layout)
+static void FillHeaderStaging(const std::vector<const CBlockHeader*>& headers, size_t solBytes, size_t lo, size_t hi,
+                              uint8_t* in, uint8_t* sols, uint8_t* lenok, WorkerPool& workers) {
+    workers.ParallelFor(
+        hi - lo,
+        [&](size_t k) {
+            const CBlockHeader& h = *headers[lo + k];
+            WriteEquihashInput(h, in + k * 140);
+            const bool ok = h.nSolution.size() == solBytes;
+            lenok[k] = ok;
+            if (ok) memcpy(sols + k * solBytes, h.nSolution.data(), solBytes);
+            else memset(sols + k * solBytes, 0, solBytes);
+        },
+        32);
+}
+
+std::vector<HeaderCheck> CheckBlockHeaders(const std::vector<const CBlockHeader*>& headers, const CChainParams& params,
+                                           bool allow_gpu) {
+    const EquihashParams ep(params.EquihashN(), params.EquihashK());
+    const Consensus::Params& cp = params.GetConsensus();
+    std::vector<HeaderCheck> out(headers.size());
+    if (headers.empty()) return out;
+    const bool deviceHashes = (ep.N == 200 && ep.K == 9) || (ep.N == 96 && ep.K == 5) || (ep.N == 48 && ep.K == 5);
+    auto cpuHash = [&](size_t i) {
+        out[i].hash = headers[i]->GetHashNew();
+        out[i].powOk = CheckProofOfWork(out[i].hash, headers[i]->nBits, true, cp);
+        out[i].hashKnown = true;
+        out[i].fromDevice = false;
+    };
+    if (allow_gpu && deviceHashes && headers.size() >= 4 && gpuFailures.load() < 3 &&
+        (GpuFaultInjection() || gpu::GpuAvailable())) {
+        try {
+            if (GpuFaultInjection()) throw std::runtime_error("injected GPU header-check fault");
+            const size_t solBytes = gpu::EquihashSolutionBytes(ep.N, ep.K);
+            auto fill = [&](size_t lo, size_t hi, uint8_t* in, uint8_t* sols, uint8_t* lenok, WorkerPool& workers) {
+                FillHeaderStaging(headers, solBytes, lo, hi, in, sols, lenok, workers);
+            };
+            const uint256 limit = cp.PowLimit(true); // 256-bit little-endian in memory
+            std::vector<uint8_t> status;
+            std::vector<unsigned char> hashes;
+            GpuVerifyService::Instance().CheckHeaders(ep.N, ep.K, headers.size(), fill, limit.begin(), status, hashes);
+            for (size_t i = 0; i < headers.size(); ++i) {
+                out[i].solutionOk = (status[i] & gpu::HDR_SOLUTION_VALID) != 0;
+                if (status[i] & gpu::HDR_HASH_VALID) {
+                    memcpy(out[i].hash.begin(), hashes.data() + 32 * i, 32);
+                    out[i].powOk = (status[i] & gpu::HDR_HASH_MEETS) != 0;
+                    out[i].hashKnown = out[i].fromDevice = true;
+                } else {
+                    cpuHash(i); // another solution length: another serialization
+                }
+            }
+            gpuFailures = 0;
+            return out;
+        } catch (const std::exception& e) {
+            const int f = ++gpuFailures;
+            LogPrintf("GPU header check failed (%s); checking %zu headers on the CPU%s\n", e.what(), headers.size(),
+                      f >= 3 ? " (GPU path now disabled)" : "");
+            out.assign(headers.size(), HeaderCheck());
+        }
+    }
+    // no device hashing (CPU node, small batch, a parameter set the device does not hash, or a
+    // failed batch): the solutions as CheckEquihashSolutions checks them, hash and target here
+    const std::vector<bool> sol = CheckEquihashSolutions(headers, params, allow_gpu && !deviceHashes);
+    for (size_t i = 0; i < headers.size(); ++i) {
+        out[i].solutionOk = sol[i];
+        cpuHash(i);
+    }
+    return out;
+}
+
 std::vector<bool> CheckEquihashSolutions(const std::vector<const CBlockHeader*>& headers, const CChainParams& params,
                                          bool allow_gpu) {
     const EquihashParams ep(params.EquihashN(), params.EquihashK());
     std::vector<bool> out(headers.size(), false);
     if (headers.empty()) return out;
-    static std::atomic<int> gpuFailures{0};
     if (allow_gpu && headers.size() >= 4 && gpuFailures.load() < 3 && (GpuFaultInjection() || gpu::GpuAvailable())) {
         // A device failure must not leave headers neither accepted nor rejected: log it and
         // verify the same batch on the CPU. Three consecutive failures turn the GPU path off.
@@ -153,17 +229,7 @@ std::vector<bool> CheckEquihashSolutions(const std::vector<const CBlockHeader*>&
             // validation GPUs (node/gpuverify.h)
             const size_t solBytes = gpu::EquihashSolutionBytes(ep.N, ep.K);
             auto fill = [&](size_t lo, size_t hi, uint8_t* in, uint8_t* sols, uint8_t* lenok, WorkerPool& workers) {
-                workers.ParallelFor(
-                    hi - lo,
-                    [&](size_t k) {
-                        const CBlockHeader& h = *headers[lo + k];
-                        WriteEquihashInput(h, in + k * 140);
-                        const bool ok = h.nSolution.size() == solBytes;
-                        lenok[k] = ok;
-                        if (ok) memcpy(sols + k * solBytes, h.nSolution.data(), solBytes);
-                        else memset(sols + k * solBytes, 0, solBytes);
-                    },
-                    32);
+                FillHeaderStaging(headers, solBytes, lo, hi, in, sols, lenok, workers);
             };
             std::vector<uint8_t> r = GpuVerifyService::Instance().EquihashHeaders(ep.N, ep.K, headers.size(), fill);
             for (size_t i = 0; i < r.size(); ++i) out[i] = r[i] != 0;

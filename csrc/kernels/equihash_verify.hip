@@ -16,6 +16,7 @@
 #include <chrono>
 
 #include "kernels/blake2b_device.h"
+#include "kernels/equihash_header.h"
 #include "kernels/gpu_api.h"
 #include "kernels/hip_util.h"
 
@@ -225,6 +226,127 @@ void VerifyLane::EquihashHeaders(unsigned N, unsigned K, size_t n,
     throw std::invalid_argument("EquihashVerifyBatch: unsupported (N,K)");
 }
 
+// ------------------------------------------------------------------ whole header checks
+static_assert(HDR_SOLUTION_VALID == bcpk::EH_HDR_SOLUTION_VALID && HDR_TARGET_LEGAL == bcpk::EH_HDR_TARGET_LEGAL &&
+                  HDR_HASH_MEETS == bcpk::EH_HDR_HASH_MEETS && HDR_HASH_VALID == bcpk::EH_HDR_HASH_VALID &&
+                  HDR_LINKED == bcpk::EH_HDR_LINKED,
+              "gpu_api.h mirrors the kernels' status bits");
+
+// The four kernels of a header batch, enqueued on `stream`: base states, eh_verify (its 0 / 1 into
+// the status bytes), hash + nBits + target (the other bits), links. Every pointer is device
+// memory; in140, sols and hashes are 4-byte aligned.
+template <class C, class P>
+static void enqueue_header_checks(hipStream_t stream, const unsigned char* d_in, const unsigned char* d_sols,
+                                  const uint8_t* d_lenok, bcpk::EhBaseState* d_states, const unsigned char powLimitLE[32],
+                                  uint8_t* d_status, uint32_t* d_hashes, size_t n) {
+    static_assert(C::SOLW == P::SOLW, "verify and hash configurations of one parameter set");
+    bcpk::EhPowTarget limit;
+    memcpy(limit.w, powLimitLE, 32);
+    const unsigned lanes = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(bcpk::eh_state_kernel, dim3(lanes), dim3(64), 0, stream, (const uint8_t*)d_in, d_states,
+                       (uint32_t)C::N, (uint32_t)C::K, (int)n);
+    BCP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((bcpk::eh_verify<C>), dim3((unsigned)n), dim3(C::NTH), 0, stream,
+                       (const bcpk::EhBaseState*)d_states, (const uint8_t*)d_sols, d_status);
+    BCP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((bcpk::eh_header_check<P>), dim3((unsigned)n), dim3(64), 0, stream,
+                       reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<const uint32_t*>(d_sols), d_lenok, limit,
+                       d_hashes, d_status);
+    BCP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bcpk::eh_header_links, dim3(lanes), dim3(64), 0, stream, reinterpret_cast<const uint32_t*>(d_in),
+                       d_lenok, (const uint32_t*)d_hashes, d_status, (int)n);
+    BCP_HIP_CHECK(hipGetLastError());
+}
+
+// `fill` as verify_lane_headers; one H2D copy (inputs, solutions, length flags), the four
+// kernels, one D2H copy of hashes + statuses.
+template <class C, class P>
+static void check_lane_headers(LaneState& L, size_t n, const std::function<void(uint8_t*, uint8_t*, uint8_t*)>& fill,
+                               const unsigned char powLimitLE[32], uint8_t* status, unsigned char* hashes,
+                               unsigned char* firstPrev32) {
+    if (n == 0) return;
+    if (n > 0x7fffffffu) throw std::invalid_argument("CheckHeaders: too many headers for one launch");
+    BCP_HIP_CHECK(hipSetDevice(L.device));
+    const size_t ib = (n * 140 + 15) & ~(size_t)15, pb = n * C::SOLW;
+    unsigned char* h_in = L.Host(0, ib + pb + n);
+    const auto t0 = std::chrono::steady_clock::now();
+    fill(h_in, h_in + ib, h_in + ib + pb);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (firstPrev32) memcpy(firstPrev32, h_in + 4, 32);
+    unsigned char* h_out = L.Host(1, n * 33);
+    unsigned char* d_in = L.Dev(0, ib + pb + n);
+    bcpk::EhBaseState* d_states = reinterpret_cast<bcpk::EhBaseState*>(L.Dev(2, n * sizeof(bcpk::EhBaseState)));
+    unsigned char* d_out = L.Dev(1, n * 33); // hashes, then statuses
+    BCP_HIP_CHECK(hipMemcpyAsync(d_in, h_in, ib + pb + n, hipMemcpyHostToDevice, L.stream));
+    enqueue_header_checks<C, P>(L.stream, d_in, d_in + ib, d_in + ib + pb, d_states, powLimitLE, d_out + n * 32,
+                                reinterpret_cast<uint32_t*>(d_out), n);
+    BCP_HIP_CHECK(hipMemcpyAsync(h_out, d_out, n * 33, hipMemcpyDeviceToHost, L.stream));
+    BCP_HIP_CHECK(hipStreamSynchronize(L.stream));
+    memcpy(hashes, h_out, n * 32);
+    memcpy(status, h_out + n * 32, n);
+    for (size_t i = 0; i < n; ++i) L.headerHashes += (status[i] & HDR_HASH_VALID) ? 1 : 0;
+    const auto t2 = std::chrono::steady_clock::now();
+    L.fillMicros += std::chrono::duration_cast<std::chrono::microseconds>(t1 - t0).count();
+    L.deviceMicros += std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count();
+    L.batches++;
+    L.items += n;
+}
+
+void VerifyLane::CheckHeaders(unsigned N, unsigned K, size_t n,
+                              const std::function<void(uint8_t*, uint8_t*, uint8_t*)>& fill,
+                              const unsigned char powLimitLE[32], uint8_t* status, unsigned char* hashes,
+                              unsigned char* firstPrev32) {
+    if (N == 200 && K == 9)
+        return check_lane_headers<bcpk::EvCfg<200, 9>, bcpk::PowCfg<200, 9>>(*impl, n, fill, powLimitLE, status, hashes, firstPrev32);
+    if (N == 96 && K == 5)
+        return check_lane_headers<bcpk::EvCfg<96, 5>, bcpk::PowCfg<96, 5>>(*impl, n, fill, powLimitLE, status, hashes, firstPrev32);
+    if (N == 48 && K == 5)
+        return check_lane_headers<bcpk::EvCfg<48, 5>, bcpk::PowCfg<48, 5>>(*impl, n, fill, powLimitLE, status, hashes, firstPrev32);
+    throw std::invalid_argument("CheckHeaders: unsupported (N,K); GPU supports (200,9),(96,5),(48,5)");
+}
+
+size_t EquihashCheckHeadersScratchBytes(size_t n) { return n * sizeof(bcpk::EhBaseState); }
+
+void EquihashCheckHeadersDevice(unsigned N, unsigned K, const void* in140, const void* sols, const void* lenok,
+                                const unsigned char powLimitLE[32], void* scratch, void* status, void* hashes, size_t n,
+                                int device, uintptr_t stream) {
+    if (n > 0x7fffffffu) throw std::invalid_argument("EquihashCheckHeadersDevice: too many headers for one launch");
+    const bool known = (N == 200 && K == 9) || (N == 96 && K == 5) || (N == 48 && K == 5);
+    if (!known)
+        throw std::invalid_argument("EquihashCheckHeadersDevice: unsupported (N,K); GPU supports (200,9),(96,5),(48,5)");
+    if (n == 0) return;
+    if (((uintptr_t)in140 | (uintptr_t)sols | (uintptr_t)hashes) & 3 || ((uintptr_t)scratch & 7))
+        throw std::invalid_argument("EquihashCheckHeadersDevice: in140, sols and hashes need 4-byte, scratch 8-byte alignment");
+    DeviceScope scope(device);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    auto* d_in = static_cast<const unsigned char*>(in140);
+    auto* d_sols = static_cast<const unsigned char*>(sols);
+    auto* d_len = static_cast<const uint8_t*>(lenok);
+    auto* d_states = static_cast<bcpk::EhBaseState*>(scratch);
+    auto* d_status = static_cast<uint8_t*>(status);
+    auto* d_hashes = static_cast<uint32_t*>(hashes);
+    if (N == 200) enqueue_header_checks<bcpk::EvCfg<200, 9>, bcpk::PowCfg<200, 9>>(st, d_in, d_sols, d_len, d_states, powLimitLE, d_status, d_hashes, n);
+    else if (N == 96) enqueue_header_checks<bcpk::EvCfg<96, 5>, bcpk::PowCfg<96, 5>>(st, d_in, d_sols, d_len, d_states, powLimitLE, d_status, d_hashes, n);
+    else enqueue_header_checks<bcpk::EvCfg<48, 5>, bcpk::PowCfg<48, 5>>(st, d_in, d_sols, d_len, d_states, powLimitLE, d_status, d_hashes, n);
+}
+
+void EquihashCompactDecodeBatch(const uint32_t* nbits, size_t n, std::vector<unsigned char>& targets_le,
+                                std::vector<uint8_t>& flags, int device) {
+    if (n > 0x7fffffffu) throw std::invalid_argument("EquihashCompactDecodeBatch: too many values for one launch");
+    DeviceScope scope(device);
+    targets_le.assign(n * 32, 0);
+    flags.assign(n, 0);
+    if (n == 0) return;
+    DevBuf<uint32_t> d_bits(n), d_t(n * 8);
+    DevBuf<uint8_t> d_f(n);
+    BCP_HIP_CHECK(hipMemcpy(d_bits.p, nbits, n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bcpk::eh_compact_decode, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0,
+                       (const uint32_t*)d_bits.p, (int)n, d_t.p, d_f.p);
+    BCP_HIP_CHECK(hipGetLastError());
+    BCP_HIP_CHECK(hipMemcpy(targets_le.data(), d_t.p, n * 32, hipMemcpyDeviceToHost));
+    BCP_HIP_CHECK(hipMemcpy(flags.data(), d_f.p, n, hipMemcpyDeviceToHost));
+}
+
 size_t EquihashSolutionBytes(unsigned N, unsigned K) { return ((size_t)1 << K) * (N / (K + 1) + 1) / 8; }
 
 VerifyLane::VerifyLane(int device, bool highPriority) : impl(new Impl) {
@@ -245,6 +367,7 @@ int VerifyLane::Device() const { return impl->device; }
 int VerifyLane::Priority() const { return impl->priority; }
 uint64_t VerifyLane::Batches() const { return impl->batches; }
 uint64_t VerifyLane::Items() const { return impl->items; }
+uint64_t VerifyLane::HeaderHashes() const { return impl->headerHashes; }
 uint64_t VerifyLane::FillMicros() const { return impl->fillMicros; }
 uint64_t VerifyLane::DeviceMicros() const { return impl->deviceMicros; }
 
@@ -283,6 +406,24 @@ std::vector<uint8_t> EquihashVerifyBatch(unsigned n, unsigned k, const std::vect
     VerifyLane& lane = DefaultLane(device, hold);
     lane.Equihash(n, k, states.data(), ptrs.data(), states.size(), result.data());
     return result;
+}
+
+void EquihashCheckHeadersBatch(unsigned n, unsigned k, const unsigned char* in140, const unsigned char* sols,
+                               const uint8_t* lenok, size_t cnt, const unsigned char powLimitLE[32],
+                               std::vector<uint8_t>& status, std::vector<unsigned char>& hashes, int device) {
+    status.assign(cnt, 0);
+    hashes.assign(cnt * 32, 0);
+    const size_t sw = EquihashSolutionBytes(n, k);
+    std::unique_lock<std::mutex> hold;
+    VerifyLane& lane = DefaultLane(device, hold);
+    lane.CheckHeaders(
+        n, k, cnt,
+        [&](uint8_t* in, uint8_t* so, uint8_t* ok) {
+            memcpy(in, in140, cnt * 140);
+            memcpy(so, sols, cnt * sw);
+            memcpy(ok, lenok, cnt);
+        },
+        powLimitLE, status.data(), hashes.data());
 }
 
 bool GpuAvailable() {

@@ -143,6 +143,21 @@ void EquihashPowCheckBatch(unsigned n, unsigned k, const unsigned char* in140, c
                            const unsigned char target_le[32], std::vector<unsigned char>& hashes,
                            std::vector<uint8_t>& pass, int device = -1);
 
+// Status bits of a header checked by VerifyLane::CheckHeaders / EquihashCheckHeadersDevice
+// (csrc/kernels/equihash_header.h): the whole of CheckBlockHeader for a post-fork header.
+enum HeaderStatus : uint8_t {
+    HDR_SOLUTION_VALID = 1, // the Equihash solution is valid (IsValidSolution)
+    HDR_TARGET_LEGAL = 2,   // nBits decodes (SetCompact) to a target in (0, pow limit], not negative, no overflow
+    HDR_HASH_MEETS = 4,     // TARGET_LEGAL and hash <= target: CheckProofOfWork
+    HDR_HASH_VALID = 8,     // the returned hash is the header's; clear where the solution has another length
+                            // (the serialization then has another length too: the caller hashes on the CPU)
+    HDR_LINKED = 16,        // hashPrevBlock equals the hash of the header before it, both hashes valid (header 0: set)
+};
+// Debug entry: arith_uint256::SetCompact on the device over n nBits values. targets_le = n x 32
+// bytes (256-bit little-endian), flags[i] = negative | overflow << 1.
+void EquihashCompactDecodeBatch(const uint32_t* nbits, size_t n, std::vector<unsigned char>& targets_le,
+                                std::vector<uint8_t>& flags, int device = -1);
+
 // --------------------------------------------------------------- SHA-256d
 // out[i] = SHA256d(in[offs[i] .. offs[i]+lens[i]))
 std::vector<unsigned char> Sha256dBatch(const std::vector<unsigned char>& data, const std::vector<uint64_t>& offs,
@@ -205,6 +220,23 @@ size_t EcdsaJobBytes();
 void EcdsaVerifyDevice(const void* msg32, const void* sig64, const void* pub33, void* jobs, void* result, size_t n,
                        int device, uintptr_t stream);
 
+// Whole header checks of n post-fork headers: in140 = n x 140 bytes (CEquihashInput || nNonce),
+// sols = n x EquihashSolutionBytes(N, K), lenok = n bytes (0: the header's solution had another
+// length; its slot's content is ignored), powLimitLE = the chain's pow limit (256-bit
+// little-endian, host memory), scratch = EquihashCheckHeadersScratchBytes(n) bytes for the
+// BLAKE2b base states (8-byte aligned), status = n HeaderStatus bytes, hashes = n x 32 bytes.
+// in140, sols and hashes are 4-byte aligned. (N, K) as EquihashPowCheckBatch; others throw.
+size_t EquihashCheckHeadersScratchBytes(size_t n);
+void EquihashCheckHeadersDevice(unsigned N, unsigned K, const void* in140, const void* sols, const void* lenok,
+                                const unsigned char powLimitLE[32], void* scratch, void* status, void* hashes, size_t n,
+                                int device, uintptr_t stream);
+
+// The same from host memory through the device's default lane (pinned staging, the lane's
+// stream, one H2D and one D2H copy): status = cnt HeaderStatus bytes, hashes = cnt x 32 bytes.
+void EquihashCheckHeadersBatch(unsigned n, unsigned k, const unsigned char* in140, const unsigned char* sols,
+                               const uint8_t* lenok, size_t cnt, const unsigned char powLimitLE[32],
+                               std::vector<uint8_t>& status, std::vector<unsigned char>& hashes, int device = -1);
+
 // --------------------------------------------------------------- verification lanes
 // A verification lane is one device plus one HIP stream (created at the device's greatest
 // priority when `highPriority`, so a validation batch is scheduled ahead of the persistent
@@ -243,6 +275,14 @@ public:
     void EquihashHeaders(unsigned N, unsigned K, size_t n,
                          const std::function<void(uint8_t* in140, uint8_t* sols, uint8_t* lenok)>& fill,
                          uint8_t* result);
+    // The whole of CheckBlockHeader for n post-fork headers from the same `fill`: status[i] =
+    // HeaderStatus bits, hashes = n x 32 bytes (zero where HDR_HASH_VALID is clear), one D2H copy
+    // for both. firstPrev32, when given, receives header 0's hashPrevBlock (a caller that splits
+    // a message over lanes links the shards with it). (N, K) as EquihashPowCheckBatch.
+    void CheckHeaders(unsigned N, unsigned K, size_t n,
+                      const std::function<void(uint8_t* in140, uint8_t* sols, uint8_t* lenok)>& fill,
+                      const unsigned char powLimitLE[32], uint8_t* status, unsigned char* hashes,
+                      unsigned char* firstPrev32 = nullptr);
     // Same contract as EquihashVerifyBatch for n (state, solution) pairs; a solution of the
     // wrong length is rejected.
     void Equihash(unsigned N, unsigned K, const EhBaseState* states, const std::vector<unsigned char>* const* sols,
@@ -250,6 +290,8 @@ public:
     // Batches and items this lane has run (service statistics).
     uint64_t Batches() const;
     uint64_t Items() const;
+    // header hashes CheckHeaders has returned (HDR_HASH_VALID set)
+    uint64_t HeaderHashes() const;
     // time spent in the callers' fills (host) and in copies + kernels + the wait (device)
     uint64_t FillMicros() const;
     uint64_t DeviceMicros() const;

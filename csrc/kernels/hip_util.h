@@ -93,6 +93,7 @@ struct LaneState {
     HostBuf<unsigned char> host[SLOTS];
     DevBuf<unsigned char> dev[SLOTS];
     uint64_t batches = 0, items = 0;
+    uint64_t headerHashes = 0; // header hashes computed on the device
     // host share (the caller's fill into pinned staging) and device share (copies, kernels and
     // the wait for them) of the batches, microseconds
     uint64_t fillMicros = 0, deviceMicros = 0;

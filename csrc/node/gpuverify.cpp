@@ -3,7 +3,9 @@
 #include "util/util.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <cstring>
 #include <exception>
 #include <cstdlib>
 #include <stdexcept>
@@ -228,6 +230,7 @@ void GpuVerifyService::RunSharded(size_t n, bool equihash,
                 (equihash ? L->equihashItems : L->ecdsaItems) += hi - lo;
                 L->fillMicros = L->gl->FillMicros(); // published for Stats() (this is the lane's thread)
                 L->deviceMicros = L->gl->DeviceMicros();
+                L->headerHashes = L->gl->HeaderHashes();
             } catch (...) {
                 e = std::current_exception();
             }
@@ -292,6 +295,32 @@ std::vector<uint8_t> GpuVerifyService::EquihashHeaders(unsigned N, unsigned K, s
     return out;
 }
 
+void GpuVerifyService::CheckHeaders(unsigned N, unsigned K, size_t n, const HeaderFillFn& fill,
+                                    const unsigned char powLimitLE[32], std::vector<uint8_t>& status,
+                                    std::vector<unsigned char>& hashes) {
+    status.assign(n, 0);
+    hashes.assign(n * 32, 0);
+    if (n == 0) return;
+    std::mutex pm;
+    std::vector<std::pair<size_t, std::array<unsigned char, 32>>> firstPrev; // (shard start, its hashPrevBlock)
+    RunSharded(n, true, [&](gpu::VerifyLane& lane, size_t lo, size_t hi, WorkerPool& workers) {
+        std::array<unsigned char, 32> prev;
+        lane.CheckHeaders(
+            N, K, hi - lo, [&](uint8_t* in, uint8_t* sols, uint8_t* lenok) { fill(lo, hi, in, sols, lenok, workers); },
+            powLimitLE, status.data() + lo, hashes.data() + lo * 32, prev.data());
+        std::lock_guard<std::mutex> l(pm);
+        firstPrev.emplace_back(lo, prev);
+    });
+    for (const auto& fp : firstPrev) {
+        const size_t lo = fp.first;
+        if (lo == 0) continue;
+        const bool linked = (status[lo] & gpu::HDR_HASH_VALID) && (status[lo - 1] & gpu::HDR_HASH_VALID) &&
+                            memcmp(fp.second.data(), hashes.data() + (lo - 1) * 32, 32) == 0;
+        if (linked) status[lo] |= gpu::HDR_LINKED;
+        else status[lo] &= (uint8_t)~gpu::HDR_LINKED;
+    }
+}
+
 std::vector<uint8_t> GpuVerifyService::Equihash(unsigned N, unsigned K, const std::vector<gpu::EhBaseState>& states,
                                                 const std::vector<const std::vector<unsigned char>*>& sols) {
     if (states.size() != sols.size()) throw std::invalid_argument("GpuVerifyService::Equihash: sizes");
@@ -315,7 +344,7 @@ std::vector<GpuVerifyService::LaneStats> GpuVerifyService::Stats() const {
     for (const auto& L : lanes) {
         out.push_back(LaneStats{L->device, L->priority.load(), L->batches.load(), L->items.load(),
                                 L->fillMicros.load(), L->deviceMicros.load(), L->ecdsaItems.load(),
-                                L->equihashItems.load()});
+                                L->equihashItems.load(), L->headerHashes.load()});
     }
     return out;
 }

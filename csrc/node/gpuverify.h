@@ -84,6 +84,12 @@ public:
     using HeaderFillFn = std::function<void(size_t lo, size_t hi, uint8_t* in140, uint8_t* sols, uint8_t* lenok,
                                             WorkerPool& workers)>;
     std::vector<uint8_t> EquihashHeaders(unsigned N, unsigned K, size_t n, const HeaderFillFn& fill);
+    // The whole of CheckBlockHeader for post-fork headers [0, n) (gpu::VerifyLane::CheckHeaders):
+    // status = n gpu::HeaderStatus bytes, hashes = n x 32 bytes. Sharded like EquihashHeaders; a
+    // lane links only the headers of its own shard, so HDR_LINKED of every later shard's first
+    // header is set here from the shard before it's last hash.
+    void CheckHeaders(unsigned N, unsigned K, size_t n, const HeaderFillFn& fill, const unsigned char powLimitLE[32],
+                      std::vector<uint8_t>& status, std::vector<unsigned char>& hashes);
     // result[i] = 1 iff solution i is valid for state i.
     std::vector<uint8_t> Equihash(unsigned N, unsigned K, const std::vector<gpu::EhBaseState>& states,
                                   const std::vector<const std::vector<unsigned char>*>& sols);
@@ -94,6 +100,7 @@ public:
         uint64_t batches, items;
         uint64_t fillMicros, deviceMicros; // host fill vs device share of the lane's batches
         uint64_t ecdsaItems, equihashItems; // items by kind (signatures / header solutions)
+        uint64_t headerHashes;              // header hashes computed on the device (CheckHeaders)
     };
     std::vector<LaneStats> Stats() const;
     uint64_t ShardedBatches() const;
@@ -113,7 +120,7 @@ private:
         std::string initError;
         std::atomic<int> priority{0};
         std::atomic<uint64_t> batches{0}, items{0};
-        std::atomic<uint64_t> ecdsaItems{0}, equihashItems{0};
+        std::atomic<uint64_t> ecdsaItems{0}, equihashItems{0}, headerHashes{0};
         std::atomic<uint64_t> fillMicros{0}, deviceMicros{0}; // the lane's host fill vs device time
         std::unique_ptr<WorkerPool> fill; // this lane's host-fill workers
     };

@@ -24,6 +24,7 @@ std::unique_ptr<NodeContext> BuildNode(const std::string& chain, const std::stri
     o.memoryOnly = memoryOnly;
     o.wipe = wipe;
     o.useGpu = useGpu;
+    o.gpuHeaderPow = gArgs.GetBoolArg("-gpuheaderpow", o.gpuHeaderPow);
     o.txindex = gArgs.GetBoolArg("-txindex", false);
     o.checkBlockIndex = gArgs.GetBoolArg("-checkblockindex", node->params->DefaultConsistencyChecks());
     o.checkpoints = gArgs.GetBoolArg("-checkpoints", true);

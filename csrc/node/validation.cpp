@@ -301,8 +301,8 @@ CBlockIndex* Chainstate::InsertBlockIndex(const uint256& hash) {
     return pindexNew;
 }
 
-CBlockIndex* Chainstate::AddToBlockIndex(const CBlockHeader& block) {
-    const uint256 hash = block.GetHash(params.GetConsensus());
+CBlockIndex* Chainstate::AddToBlockIndex(const CBlockHeader& block, const uint256* knownHash) {
+    const uint256 hash = knownHash ? *knownHash : block.GetHash(params.GetConsensus());
     auto it = mapBlockIndex.find(hash);
     if (it != mapBlockIndex.end()) return it->second;
     blockIndexStorage.emplace_back(new CBlockIndex(block));
@@ -495,8 +495,8 @@ bool Chainstate::ContextualCheckBlock(const CBlock& block, CValidationState& sta
 
 // ------------------------------------------------------------------ header / block acceptance
 bool Chainstate::AcceptBlockHeader(const CBlockHeader& block, CValidationState& state, CBlockIndex** ppindex,
-                                   bool equihashChecked) {
-    const uint256 hash = block.GetHash(params.GetConsensus());
+                                   bool equihashChecked, const uint256* knownHash, const bool* powOk) {
+    const uint256 hash = knownHash ? *knownHash : block.GetHash(params.GetConsensus());
     CBlockIndex* pindex = nullptr;
     if (hash != params.GetConsensus().hashGenesisBlock) {
         auto miSelf = mapBlockIndex.find(hash);
@@ -510,7 +510,7 @@ bool Chainstate::AcceptBlockHeader(const CBlockHeader& block, CValidationState& 
         }
         if (equihashChecked) {
             const bool postfork = IsBCPEnabled((int)block.nHeight);
-            if (!CheckProofOfWork(hash, block.nBits, postfork, params.GetConsensus()))
+            if (!(powOk ? *powOk : CheckProofOfWork(hash, block.nBits, postfork, params.GetConsensus())))
                 return state.DoS(50, false, REJECT_INVALID, "high-hash", false, "proof of work failed");
         } else if (!CheckBlockHeader(block, state)) {
             return error("%s: Consensus::CheckBlockHeader: %s, %s", __func__, hash.ToString().c_str(),
@@ -527,7 +527,7 @@ bool Chainstate::AcceptBlockHeader(const CBlockHeader& block, CValidationState& 
             return error("%s: Consensus::ContextualCheckBlockHeader: %s, %s", __func__, hash.ToString().c_str(),
                          FormatStateMessage(state).c_str());
     }
-    if (pindex == nullptr) pindex = AddToBlockIndex(block);
+    if (pindex == nullptr) pindex = AddToBlockIndex(block, &hash);
     if (ppindex) *ppindex = pindex;
     CheckBlockIndex();
     return true;
@@ -554,6 +554,48 @@ void Chainstate::NotifyHeaderTip() {
 
 bool Chainstate::ProcessNewBlockHeaders(const std::vector<CBlockHeader>& headers, CValidationState& state,
                                         const CBlockIndex** ppindex) {
+    // With the GPU, every post-fork header of a message goes to the device, known or not: one pass
+    // returns solution verdict, hash and proof of work (CheckBlockHeaders), so no header is hashed
+    // here. Blocks that arrive singly and small messages take the per-header path.
+    std::vector<const CBlockHeader*> toCheck;
+    std::vector<size_t> pos;
+    if (opts.useGpu && opts.gpuHeaderPow) {
+        for (size_t i = 0; i < headers.size(); i++) {
+            if (!IsBCPEnabled((int)headers[i].nHeight)) continue;
+            toCheck.push_back(&headers[i]);
+            pos.push_back(i);
+        }
+    }
+    if (toCheck.size() < 4) return ProcessNewBlockHeadersPerHeader(headers, state, ppindex);
+    const std::vector<HeaderCheck> res = CheckBlockHeaders(toCheck, params, true);
+    {
+        std::lock_guard<CCriticalSection> l(cs_main);
+        std::vector<const HeaderCheck*> at(headers.size(), nullptr);
+        std::vector<bool> eqOk(headers.size(), true);
+        // a header already in the index (before any of this message is accepted) keeps whatever
+        // its solution is, as the per-header path's skip does
+        for (size_t j = 0; j < res.size(); j++) {
+            at[pos[j]] = &res[j];
+            eqOk[pos[j]] = res[j].solutionOk || mapBlockIndex.count(res[j].hash) != 0;
+        }
+        for (size_t i = 0; i < headers.size(); i++) {
+            if (!eqOk[i])
+                return state.DoS(100, error("ProcessNewBlockHeaders(): Equihash solution invalid"), REJECT_INVALID,
+                                 "invalid-solution");
+            CBlockIndex* pindex = nullptr;
+            const HeaderCheck* hc = at[i];
+            if (!AcceptBlockHeader(headers[i], state, &pindex, IsBCPEnabled((int)headers[i].nHeight),
+                                   hc ? &hc->hash : nullptr, hc ? &hc->powOk : nullptr))
+                return false;
+            if (ppindex) *ppindex = pindex;
+        }
+    }
+    NotifyHeaderTip();
+    return true;
+}
+
+bool Chainstate::ProcessNewBlockHeadersPerHeader(const std::vector<CBlockHeader>& headers, CValidationState& state,
+                                                 const CBlockIndex** ppindex) {
     // Batch the Equihash checks of unknown post-fork headers (GPU when >= 4 headers).
     std::vector<const CBlockHeader*> toCheck;
     std::vector<size_t> pos;

@@ -84,6 +84,7 @@ struct ChainstateOptions {
     bool txindex = false;
     int scriptThreads = 0;          // <= 0: auto (cores)
     bool useGpu = true;             // batch ECDSA + header Equihash verification on the GPU
+    bool gpuHeaderPow = true;       // -gpuheaderpow: header hash + proof of work in the same device pass
     bool checkBlockIndex = false;   // -checkblockindex (expensive consistency checks)
     bool checkpoints = true;
     uint64_t maxBlockSize = DEFAULT_MAX_BLOCK_SIZE;
@@ -274,9 +275,17 @@ private:
     };
 
     CBlockIndex* InsertBlockIndex(const uint256& hash) EXCLUSIVE_LOCKS_REQUIRED(cs_main);
-    CBlockIndex* AddToBlockIndex(const CBlockHeader& block) EXCLUSIVE_LOCKS_REQUIRED(cs_main);
+    // knownHash: the header's hash where the caller has it already
+    CBlockIndex* AddToBlockIndex(const CBlockHeader& block, const uint256* knownHash = nullptr)
+        EXCLUSIVE_LOCKS_REQUIRED(cs_main);
+    // knownHash: the header's hash where the caller has it already; powOk: the verdict of
+    // CheckProofOfWork on that hash where the caller has that too (both from a header batch).
     bool AcceptBlockHeader(const CBlockHeader& block, CValidationState& state, CBlockIndex** ppindex,
-                           bool skipPow = false) EXCLUSIVE_LOCKS_REQUIRED(cs_main);
+                           bool skipPow = false, const uint256* knownHash = nullptr,
+                           const bool* powOk = nullptr) EXCLUSIVE_LOCKS_REQUIRED(cs_main);
+    // today's path of ProcessNewBlockHeaders: the host hashes, the batch checks only solutions
+    bool ProcessNewBlockHeadersPerHeader(const std::vector<CBlockHeader>& headers, CValidationState& state,
+                                         const CBlockIndex** ppindex);
     bool AcceptBlock(const std::shared_ptr<const CBlock>& pblock, CValidationState& state, CBlockIndex** ppindex,
                      bool fRequested, const CDiskBlockPos* dbp, bool* fNewBlock) EXCLUSIVE_LOCKS_REQUIRED(cs_main);
     bool ReceivedBlockTransactions(const CBlock& block, CValidationState& state, CBlockIndex* pindexNew,

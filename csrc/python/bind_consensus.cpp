@@ -5,6 +5,7 @@
 #include "crypto/common.h"
 #include "consensus/merkle.h"
 #include "consensus/params.h"
+#include "consensus/equihash.h"
 #include "consensus/pow.h"
 #include "keys/key.h"
 #include "primitives/block.h"
@@ -207,6 +208,78 @@ void bind_consensus(pyb::module_& m) {
             return CheckEquihashSolutions(ptrs, Params(chain), allow_gpu);
         },
         pyb::arg("headers"), pyb::arg("chain") = "regtest", pyb::arg("allow_gpu") = true);
+    // Batched CheckBlockHeader (CheckBlockHeaders): [(solution ok, pow ok, hash32, from device)].
+    m.def(
+        "check_block_headers",
+        [](const std::vector<pyb::bytes>& hs, const std::string& chain, bool allow_gpu) {
+            std::vector<CBlockHeader> headers(hs.size());
+            for (size_t i = 0; i < hs.size(); ++i) {
+                std::vector<unsigned char> v = to_vec(hs[i]);
+                SpanReader r(v.data(), v.size(), SER_NETWORK, PROTOCOL_VERSION);
+                r >> headers[i];
+            }
+            std::vector<const CBlockHeader*> ptrs;
+            for (auto& h : headers) ptrs.push_back(&h);
+            std::vector<HeaderCheck> res;
+            {
+                pyb::gil_scoped_release nogil;
+                res = CheckBlockHeaders(ptrs, Params(chain), allow_gpu);
+            }
+            pyb::list out;
+            for (const HeaderCheck& c : res)
+                out.append(pyb::make_tuple(c.solutionOk, c.powOk, to_bytes(c.hash.begin(), 32), c.fromDevice));
+            return out;
+        },
+        pyb::arg("headers"), pyb::arg("chain") = "regtest", pyb::arg("allow_gpu") = true);
+    // CPU twin of the device's header check, from the consensus code: EhIsValidSolution, the
+    // header's GetHash and CheckProofOfWork against `pow_limit` (32 bytes little-endian), plus the
+    // link to the header before. Returns ([status], [hash32]) with gpu::HeaderStatus bits.
+    m.def(
+        "eh_check_headers_cpu",
+        [](unsigned n, unsigned k, const std::vector<pyb::bytes>& in140s, const std::vector<pyb::bytes>& sols,
+           const pyb::bytes& pow_limit) {
+            const auto lim = to_vec(pow_limit);
+            if (in140s.size() != sols.size() || lim.size() != 32)
+                throw std::invalid_argument("eh_check_headers_cpu: one solution per input, 32-byte pow limit");
+            uint256 limit;
+            memcpy(limit.begin(), lim.data(), 32);
+            const EquihashParams ep(n, k);
+            const size_t sw = ((size_t)1 << k) * (n / (k + 1) + 1) / 8;
+            std::vector<int> status;
+            pyb::list hashes;
+            uint256 prevHash;
+            bool prevValid = false;
+            for (size_t i = 0; i < sols.size(); ++i) {
+                const auto in = to_vec(in140s[i]);
+                if (in.size() != 140) throw std::invalid_argument("eh_check_headers_cpu: inputs are 140 bytes");
+                std::vector<unsigned char> ser(in);
+                ser.push_back(0); // an empty solution; the real one is set below
+                SpanReader r(ser.data(), ser.size(), SER_NETWORK, PROTOCOL_VERSION);
+                CBlockHeader h;
+                r >> h;
+                h.nSolution = to_vec(sols[i]);
+                CBlake2b st = EhInitialiseState(ep);
+                st.Write(in.data(), in.size());
+                bool fNegative, fOverflow;
+                arith_uint256 target;
+                target.SetCompact(h.nBits, &fNegative, &fOverflow);
+                const bool legal = !(fNegative || target == 0 || fOverflow || target > UintToArith256(limit));
+                const bool valid = h.nSolution.size() == sw;
+                const uint256 hash = valid ? h.GetHashNew() : uint256();
+                int s = 0;
+                if (EhIsValidSolution(ep, st, h.nSolution)) s |= 1;
+                if (legal) s |= 2;
+                if (valid && CheckProofOfWork(hash, h.nBits, UintToArith256(limit))) s |= 4;
+                if (valid) s |= 8;
+                if (i == 0 || (valid && prevValid && h.hashPrevBlock == prevHash)) s |= 16;
+                status.push_back(s);
+                hashes.append(to_bytes(hash.begin(), 32));
+                prevHash = hash;
+                prevValid = valid;
+            }
+            return pyb::make_tuple(status, hashes);
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("in140s"), pyb::arg("solutions"), pyb::arg("pow_limit"));
     m.def("tx_decode", [](const pyb::bytes& b) {
         std::vector<unsigned char> v = to_vec(b);
         SpanReader r(v.data(), v.size(), SER_NETWORK, PROTOCOL_VERSION);

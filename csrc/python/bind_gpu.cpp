@@ -244,6 +244,106 @@ void bind_gpu(pyb::module_& m) {
         pyb::arg("n"), pyb::arg("k"), pyb::arg("in140s"), pyb::arg("solutions"), pyb::arg("target32"),
         pyb::arg("device") = -1);
 
+    // Whole header checks (csrc/kernels/equihash_header.h): packs (140-byte input, solution) pairs;
+    // a solution of another length gets lenok = 0. Returns ([status], [hash32]).
+    struct PackedHeaders {
+        std::vector<unsigned char> in, so;
+        std::vector<uint8_t> lenok;
+        std::vector<unsigned char> limit;
+    };
+    static const auto pack_headers = [](unsigned n, unsigned k, const std::vector<pyb::bytes>& in140s,
+                                        const std::vector<pyb::bytes>& sols, const pyb::bytes& pow_limit) {
+        PackedHeaders p;
+        const size_t sw = gpu::EquihashSolutionBytes(n, k);
+        p.limit = to_vec(pow_limit);
+        if (in140s.size() != sols.size() || p.limit.size() != 32)
+            throw std::invalid_argument("eh_check_headers: one solution per input, 32-byte pow limit");
+        p.so.assign(sols.size() * sw, 0);
+        for (size_t i = 0; i < sols.size(); ++i) {
+            const auto a = to_vec(in140s[i]), b = to_vec(sols[i]);
+            if (a.size() != 140) throw std::invalid_argument("eh_check_headers: inputs are 140 bytes");
+            p.in.insert(p.in.end(), a.begin(), a.end());
+            p.lenok.push_back(b.size() == sw);
+            if (b.size() == sw) memcpy(p.so.data() + i * sw, b.data(), sw);
+        }
+        return p;
+    };
+    static const auto headers_result = [](const std::vector<uint8_t>& status, const std::vector<unsigned char>& hashes) {
+        pyb::list hl;
+        for (size_t i = 0; i < status.size(); ++i) hl.append(to_bytes(hashes.data() + 32 * i, 32));
+        return pyb::make_tuple(std::vector<int>(status.begin(), status.end()), hl);
+    };
+    m.def(
+        "eh_check_headers_gpu",
+        [](unsigned n, unsigned k, const std::vector<pyb::bytes>& in140s, const std::vector<pyb::bytes>& sols,
+           const pyb::bytes& pow_limit, int device) {
+            const PackedHeaders p = pack_headers(n, k, in140s, sols, pow_limit);
+            std::vector<uint8_t> status;
+            std::vector<unsigned char> hashes;
+            {
+                pyb::gil_scoped_release rel;
+                gpu::EquihashCheckHeadersBatch(n, k, p.in.data(), p.so.data(), p.lenok.data(), p.lenok.size(),
+                                               p.limit.data(), status, hashes, device);
+            }
+            return headers_result(status, hashes);
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("in140s"), pyb::arg("solutions"), pyb::arg("pow_limit"),
+        pyb::arg("device") = -1);
+    // the same through the node's verify service (sharded over its lanes)
+    m.def(
+        "gpu_verify_check_headers",
+        [](unsigned n, unsigned k, const std::vector<pyb::bytes>& in140s, const std::vector<pyb::bytes>& sols,
+           const pyb::bytes& pow_limit) {
+            const PackedHeaders p = pack_headers(n, k, in140s, sols, pow_limit);
+            const size_t sw = gpu::EquihashSolutionBytes(n, k);
+            std::vector<uint8_t> status;
+            std::vector<unsigned char> hashes;
+            {
+                pyb::gil_scoped_release rel;
+                GpuVerifyService::Instance().CheckHeaders(
+                    n, k, p.lenok.size(),
+                    [&](size_t lo, size_t hi, uint8_t* in, uint8_t* so, uint8_t* ok, WorkerPool&) {
+                        memcpy(in, p.in.data() + lo * 140, (hi - lo) * 140);
+                        memcpy(so, p.so.data() + lo * sw, (hi - lo) * sw);
+                        memcpy(ok, p.lenok.data() + lo, hi - lo);
+                    },
+                    p.limit.data(), status, hashes);
+            }
+            return headers_result(status, hashes);
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("in140s"), pyb::arg("solutions"), pyb::arg("pow_limit"));
+    m.def("eh_check_headers_scratch_bytes", &gpu::EquihashCheckHeadersScratchBytes, pyb::arg("n"));
+    m.def(
+        "eh_check_headers_device",
+        [](unsigned n, unsigned k, uintptr_t in140, uintptr_t sols, uintptr_t lenok, const pyb::bytes& pow_limit,
+           uintptr_t scratch, uintptr_t status, uintptr_t hashes, size_t count, int device, uintptr_t stream) {
+            const auto limit = to_vec(pow_limit);
+            if (limit.size() != 32) throw std::invalid_argument("eh_check_headers_device: 32-byte pow limit");
+            gpu::EquihashCheckHeadersDevice(n, k, reinterpret_cast<const void*>(in140), reinterpret_cast<const void*>(sols),
+                                            reinterpret_cast<const void*>(lenok), limit.data(),
+                                            reinterpret_cast<void*>(scratch), reinterpret_cast<void*>(status),
+                                            reinterpret_cast<void*>(hashes), count, device, stream);
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("in140_ptr"), pyb::arg("sols_ptr"), pyb::arg("lenok_ptr"),
+        pyb::arg("pow_limit"), pyb::arg("scratch_ptr"), pyb::arg("status_ptr"), pyb::arg("hashes_ptr"), pyb::arg("count"),
+        pyb::arg("device"), pyb::arg("stream"));
+    // debug: SetCompact on the device -> [(target32 little-endian, negative, overflow)]
+    m.def(
+        "eh_compact_decode_gpu",
+        [](const std::vector<uint32_t>& nbits, int device) {
+            std::vector<unsigned char> targets;
+            std::vector<uint8_t> flags;
+            {
+                pyb::gil_scoped_release rel;
+                gpu::EquihashCompactDecodeBatch(nbits.data(), nbits.size(), targets, flags, device);
+            }
+            pyb::list out;
+            for (size_t i = 0; i < nbits.size(); ++i)
+                out.append(pyb::make_tuple(to_bytes(targets.data() + 32 * i, 32), (flags[i] & 1) != 0, (flags[i] & 2) != 0));
+            return out;
+        },
+        pyb::arg("nbits"), pyb::arg("device") = -1);
+
     m.def(
         "eh_verify_batch_gpu",
         [](unsigned n, unsigned k, const std::vector<CBlake2b>& sts, const std::vector<pyb::bytes>& sols, int device) {
@@ -449,6 +549,7 @@ void bind_gpu(pyb::module_& m) {
             d["items"] = L.items;
             d["fill_us"] = L.fillMicros;
             d["device_us"] = L.deviceMicros;
+            d["header_hashes"] = L.headerHashes;
             lanes.append(d);
         }
         pyb::dict out;

@@ -133,6 +133,7 @@ static UniValue getgpuinfo(const JSONRPCRequest& req) {
         o.pushKV("items", L.items);
         o.pushKV("ecdsa_items", L.ecdsaItems);
         o.pushKV("equihash_items", L.equihashItems);
+        o.pushKV("header_hashes", L.headerHashes);
         lanes.push_back(o);
     }
     obj.pushKV("validation_lanes", lanes);

@@ -22,6 +22,7 @@
 #include "node/sigverify.h"
 #include "node/gpuverify.h"
 #include "consensus/pow.h"
+#include "crypto/common.h"
 #include "consensus/equihash.h"
 #include "secp256k1/secp256k1.h"
 #include "node/txmempool.h"
@@ -1316,6 +1317,152 @@ static void IbdPipeline_Seq_GPU(State& st) {
 BENCHMARK(IbdPipeline_Seq_CPU);
 BENCHMARK(IbdPipeline_Seq_GPU);
 
+// ---- a HEADERS message of 2,000 Equihash(200,9) headers through ProcessNewBlockHeaders, end to
+// end: the per-header path (the host hashes every header for the known-header skip and again in
+// AcceptBlockHeader; the device checks only the solutions) against -gpuheaderpow=1 (solution,
+// hash and proof of work in one device pass, csrc/kernels/equihash_header.h). The chain is
+// regtest with the main network's Equihash parameters and the fork at height 1, so 2,000 real
+// headers can be mined: built once with the GPU solver (about half of all solutions meet the
+// regtest limit) and kept in -headerscache=<file> for later runs. Each iteration feeds the
+// message to a fresh in-memory chainstate; the arms alternate run by run (odd: on, even: off)
+// and only the ProcessNewBlockHeaders call is timed. -headerpow=0|1 pins one arm.
+namespace {
+struct HeaderBenchParams : CChainParams {
+    explicit HeaderBenchParams(const CChainParams& regtest) : CChainParams(regtest) {
+        nEquihashN = 200;
+        nEquihashK = 9;
+        consensus.BCPHeight = 1;
+    }
+};
+
+std::vector<CBlockHeader> HeaderMessage(const CChainParams& params, size_t count) {
+    const std::string cache = gArgs.GetArg("-headerscache", "/tmp/bench_bcp_headers_200_9.bin");
+    std::vector<CBlockHeader> out;
+    {
+        std::ifstream f(cache, std::ios::binary);
+        std::vector<unsigned char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        if (!raw.empty()) {
+            try {
+                SpanReader r(raw.data(), raw.size(), SER_NETWORK, PROTOCOL_VERSION);
+                r >> out;
+            } catch (const std::exception&) {
+                out.clear();
+            }
+        }
+        if (out.size() == count && out[0].hashPrevBlock == params.GenesisBlock().GetHash(params.GetConsensus())) return out;
+        out.clear();
+    }
+    gpu::EquihashGpuSolver solver(200, 9, 4, 0);
+    uint256 prev = params.GenesisBlock().GetHash(params.GetConsensus());
+    const uint256 limit = params.GetConsensus().PowLimit(true);
+    FastRandomContext rng(true);
+    for (size_t i = 0; i < count; i++) {
+        CBlockHeader h;
+        h.nVersion = 4;
+        h.hashPrevBlock = prev;
+        h.hashMerkleRoot = rng.rand256();
+        h.nHeight = (uint32_t)(i + 1);
+        h.nTime = params.GenesisBlock().nTime + 1 + (uint32_t)i;
+        h.nBits = params.GenesisBlock().nBits;
+        const std::vector<unsigned char> in = h.EquihashInput();
+        gpu::EhPowJob job;
+        if (in.size() != sizeof(job.prefix)) throw std::runtime_error("bench: Equihash input size");
+        memcpy(job.prefix, in.data(), in.size());
+        memcpy(job.target_le, limit.begin(), 32);
+        job.count = 4;
+        bool found = false;
+        for (uint32_t first = 0; !found && first < 4096; first += 4) {
+            memset(job.nonce_first, 0, 32);
+            WriteLE32(job.nonce_first, first);
+            solver.LaunchPow(job);
+            const gpu::EhPowResult r = solver.CollectPow();
+            if (r.hits.empty()) continue;
+            memcpy(h.nNonce.begin(), r.hits[0].nonce, 32);
+            h.nSolution = r.hits[0].solution;
+            found = true;
+        }
+        if (!found) throw std::runtime_error("bench: no solution under the regtest limit");
+        prev = h.GetHash(params.GetConsensus());
+        out.push_back(h);
+        if (i % 500 == 499) fprintf(stderr, "# header message: %zu/%zu headers mined\n", i + 1, count);
+    }
+    std::vector<unsigned char> raw;
+    VectorWriter w(raw);
+    w << out;
+    std::ofstream f(cache, std::ios::binary);
+    f.write((const char*)raw.data(), (std::streamsize)raw.size());
+    return out;
+}
+} // namespace
+
+static void Headers2000_ProcessNewBlockHeaders(State& st) {
+    if (!gpu::GpuAvailable()) return;
+    static const HeaderBenchParams params(Params("regtest"));
+    static const std::vector<CBlockHeader> headers = HeaderMessage(params, 2000);
+    const int64_t pin = gArgs.GetArg("-headerpow", (int64_t)-1);
+    std::vector<double> ms[2];
+    uint64_t fill[2] = {0, 0}, dev[2] = {0, 0}, fromDevice[2] = {0, 0};
+    GpuVerifyService& svc = GpuVerifyService::Instance();
+    auto totals = [&](uint64_t& f, uint64_t& d, uint64_t& h) {
+        f = d = h = 0;
+        for (const auto& L : svc.Stats()) {
+            f += L.fillMicros;
+            d += L.deviceMicros;
+            h += L.headerHashes;
+        }
+    };
+    int iters = 0;
+    uint256 tip;
+    while (st.KeepRunning()) {
+        ChainstateOptions o;
+        o.memoryOnly = true;
+        char tmpl[] = "/tmp/bench_bcp_headers_XXXXXX";
+        if (!mkdtemp(tmpl)) throw std::runtime_error("bench: mkdtemp failed");
+        o.datadir = tmpl;
+        o.useGpu = true;
+        o.checkpoints = false;
+        const int arm = pin >= 0 ? (pin != 0) : iters % 2;
+        o.gpuHeaderPow = arm != 0;
+        {
+            Chainstate cs(params, o);
+            std::string err;
+            if (!cs.InitBlockIndex(err)) throw std::runtime_error("bench: " + err);
+            uint64_t f0, d0, h0, f1, d1, h1;
+            totals(f0, d0, h0);
+            CValidationState hs;
+            const CBlockIndex* last = nullptr;
+            const int64_t t0 = GetTimeMicros();
+            const bool ok = cs.ProcessNewBlockHeaders(headers, hs, &last);
+            const int64_t t1 = GetTimeMicros();
+            if (!ok || !last || last->nHeight != (int)headers.size())
+                throw std::runtime_error("bench: headers " + FormatStateMessage(hs));
+            if (iters > 0 && tip != last->GetBlockHash()) throw std::runtime_error("bench: the arms disagree on the tip");
+            tip = last->GetBlockHash();
+            totals(f1, d1, h1);
+            if (iters >= 2) { // the first run of each arm starts the lanes and grows their buffers
+                ms[arm].push_back((t1 - t0) / 1000.0);
+                fill[arm] += f1 - f0;
+                dev[arm] += d1 - d0;
+                fromDevice[arm] += h1 - h0;
+            }
+        }
+        const std::string cmd = std::string("rm -rf '") + tmpl + "'";
+        if (system(cmd.c_str()) != 0) {}
+        iters++;
+    }
+    for (int arm = 0; arm < 2; arm++) {
+        std::vector<double>& v = ms[arm];
+        if (v.empty()) continue;
+        std::sort(v.begin(), v.end());
+        const double n = (double)v.size();
+        printf("# headers2000 gpuheaderpow=%d: runs %zu, ProcessNewBlockHeaders median %.3f ms (min %.3f, max %.3f), "
+               "lane fill %.3f ms, lane device %.3f ms, device hashes %.0f per run\n",
+               arm, v.size(), v[v.size() / 2], v.front(), v.back(), fill[arm] / 1000.0 / n, dev[arm] / 1000.0 / n,
+               fromDevice[arm] / n);
+    }
+}
+BENCHMARK(Headers2000_ProcessNewBlockHeaders);
+
 int main(int argc, char* argv[]) {
     gArgs.ParseParameters(argc, argv);
     if (gArgs.IsArgSet("-?") || gArgs.IsArgSet("-h") || gArgs.IsArgSet("-help")) {
@@ -1324,7 +1471,9 @@ int main(int argc, char* argv[]) {
                "                 [-parallelutxo=<min txs>] [-ecdsaminshard=<signatures>] [-debug=<category>]\n"
                "                 [-shardplan] (print the GPU verify shard plans for 1, 2 and 8 devices)\n"
                "                 [-connectinplace=0|1] [-connectlookahead=0|1] [-ibdab=inplace|lookahead]\n"
-               "                 (IBD: alternate one of those options run by run) [-tipcoins=<n>]\n");
+               "                 (IBD: alternate one of those options run by run) [-tipcoins=<n>]\n"
+               "                 [-headerpow=0|1] (Headers2000: pin -gpuheaderpow instead of alternating it)\n"
+               "                 [-headerscache=<file>] (Headers2000: where the mined header message is kept)\n");
         return 0;
     }
     { // default: <dir of the binary>/../bench/data, so the working directory does not matter
