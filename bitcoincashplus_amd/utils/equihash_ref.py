@@ -88,6 +88,61 @@ def is_valid_solution(n: int, k: int, data: bytes, soln: bytes) -> bool:
     return all(c == 0 for c in rows[0][0])
 
 
+COLLISION, ORDER, DUP, FINAL, LENGTH = 1, 2, 4, 8, 16
+
+_LEAVES = {}  # (n, k, data) -> {index: the leaf's n-bit hash slice as an integer}
+
+
+def leaf_value(n: int, k: int, data: bytes, index: int) -> int:
+    """The n-bit string of leaf `index` (digit 0 in the top bits), cached per (header, index)."""
+    entry = _LEAVES.get((n, k, data))
+    if entry is None:
+        if len(_LEAVES) >= 64:  # a test module's headers; the map does not grow without bound
+            _LEAVES.clear()
+        entry = _LEAVES[(n, k, data)] = (base_hasher(n, k, data), {})
+    base, leaves = entry
+    v = leaves.get(index)
+    if v is None:
+        iph = 512 // n
+        h = generate_hash(base, index // iph)
+        for s in range(iph):
+            leaves[index - index % iph + s] = int.from_bytes(h[s * n // 8:(s + 1) * n // 8], "big")
+        v = leaves[index]
+    return v
+
+
+def check_mask(n: int, k: int, data: bytes, soln: bytes) -> int:
+    """Which properties of a valid solution `soln` lacks, all of them evaluated (no early exit);
+    0 iff is_valid_solution. With X(node) the XOR of the leaf strings under a node and digit d
+    the d-th group of n/(k+1) bits:
+      COLLISION  some node at level l (children of 2^l leaves): digit l of X(left) != digit l of X(right)
+      ORDER      some node: first index of its left child >= first index of its right child
+      DUP        two positions hold the same index
+      FINAL      digit k of X(root) != 0
+      LENGTH     wrong byte length; nothing else is evaluated
+    """
+    cbl = n // (k + 1)
+    if len(soln) != (1 << k) * (cbl + 1) // 8:
+        return LENGTH
+    idx = indices_from_minimal(soln, cbl)
+    mask = DUP if len(set(idx)) != len(idx) else 0
+    xs = [leaf_value(n, k, data, i) for i in idx]
+    firsts = idx
+    digit = (1 << cbl) - 1
+    for level in range(k):
+        shift = n - (level + 1) * cbl
+        for a in range(0, len(xs), 2):
+            if ((xs[a] ^ xs[a + 1]) >> shift) & digit:
+                mask |= COLLISION
+            if firsts[a] >= firsts[a + 1]:
+                mask |= ORDER
+        xs = [xs[a] ^ xs[a + 1] for a in range(0, len(xs), 2)]
+        firsts = firsts[0::2]
+    if (xs[0] >> (n - (k + 1) * cbl)) & digit:
+        mask |= FINAL
+    return mask
+
+
 def solve(n: int, k: int, data: bytes) -> List[bytes]:
     """Full-index-list Wagner solver (reference BasicSolve semantics). Small params only."""
     cbl = n // (k + 1)

@@ -49,7 +49,8 @@ template <class C> __device__ __forceinline__ uint32_t stream_bits(const uint32_
 
 template <class C>
 __global__ __launch_bounds__(C::NTH) void eh_verify(const EhBaseState* __restrict__ states,
-                                                   const uint8_t* __restrict__ sols, uint8_t* __restrict__ ok) {
+                                                   const uint8_t* __restrict__ sols, uint8_t* __restrict__ ok,
+                                                   uint8_t* __restrict__ why) {
     constexpr int L = C::L, SW = C::SW;
     __shared__ uint32_t S[L][SW + 1];
     __shared__ uint32_t first[L];
@@ -130,7 +131,10 @@ __global__ __launch_bounds__(C::NTH) void eh_verify(const EhBaseState* __restric
     if (t + 1 < L && srt[t] == srt[t + 1]) atomicOr(&bad, 4u);
     if (t == 0 && stream_bits<C>(S[0], C::K * C::DB, C::DB) != 0) atomicOr(&bad, 8u);
     __syncthreads();
-    if (t == 0) ok[item] = bad ? 0 : 1;
+    if (t == 0) {
+        ok[item] = bad ? 0 : 1;
+        if (why) why[item] = (uint8_t)bad; // EhVerifyReason bits; production launches pass nullptr
+    }
 }
 
 // One lane per header: the base state from the raw 140-byte Equihash input (header prep on the
@@ -150,15 +154,18 @@ namespace bcp {
 namespace gpu {
 
 // Stages n (state, solution) pairs through the lane's pinned buffers: one H2D copy of the
-// packed states + solutions, one kernel (one workgroup per solution), one D2H copy.
+// packed states + solutions, one kernel (one workgroup per solution), one D2H copy. With `why`
+// (EquihashVerifyReasons only) the kernel also stores each item's reason mask behind the
+// verdicts, and the same copy brings both back.
 template <class C>
 static void verify_lane(LaneState& L, const EhBaseState* states, const std::vector<unsigned char>* const* sols,
-                        size_t n, uint8_t* result) {
+                        size_t n, uint8_t* result, uint8_t* why = nullptr) {
     if (n == 0) return;
     BCP_HIP_CHECK(hipSetDevice(L.device));
     const size_t sb = n * sizeof(EhBaseState), pb = n * C::SOLW;
     unsigned char* h_in = L.Host(0, sb + pb);
-    uint8_t* h_ok = L.Host(1, n);
+    const size_t ob = why ? 2 * n : n;
+    uint8_t* h_ok = L.Host(1, ob);
     memcpy(h_in, states, sb);
     std::vector<char> lenok(n, 0);
     for (size_t i = 0; i < n; ++i) {
@@ -171,14 +178,17 @@ static void verify_lane(LaneState& L, const EhBaseState* states, const std::vect
         }
     }
     unsigned char* d_in = L.Dev(0, sb + pb);
-    uint8_t* d_ok = L.Dev(1, n);
+    uint8_t* d_ok = L.Dev(1, ob);
+    uint8_t* d_why = why ? d_ok + n : nullptr;
     BCP_HIP_CHECK(hipMemcpyAsync(d_in, h_in, sb + pb, hipMemcpyHostToDevice, L.stream));
     hipLaunchKernelGGL((bcpk::eh_verify<C>), dim3(n), dim3(C::NTH), 0, L.stream,
-                       reinterpret_cast<const bcpk::EhBaseState*>(d_in), (const uint8_t*)(d_in + sb), d_ok);
+                       reinterpret_cast<const bcpk::EhBaseState*>(d_in), (const uint8_t*)(d_in + sb), d_ok, d_why);
     BCP_HIP_CHECK(hipGetLastError());
-    BCP_HIP_CHECK(hipMemcpyAsync(h_ok, d_ok, n, hipMemcpyDeviceToHost, L.stream));
+    BCP_HIP_CHECK(hipMemcpyAsync(h_ok, d_ok, ob, hipMemcpyDeviceToHost, L.stream));
     BCP_HIP_CHECK(hipStreamSynchronize(L.stream));
     for (size_t i = 0; i < n; ++i) result[i] = lenok[i] ? h_ok[i] : 0; // reference: invalid solution length
+    if (why)
+        for (size_t i = 0; i < n; ++i) why[i] = lenok[i] ? h_ok[n + i] : (uint8_t)EH_WHY_LENGTH;
     L.batches++;
     L.items += n;
 }
@@ -205,7 +215,7 @@ static void verify_lane_headers(LaneState& L, size_t n, const std::function<void
                        (const uint8_t*)d_in, d_states, (uint32_t)C::N, (uint32_t)C::K, (int)n);
     BCP_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((bcpk::eh_verify<C>), dim3(n), dim3(C::NTH), 0, L.stream, (const bcpk::EhBaseState*)d_states,
-                       (const uint8_t*)(d_in + ib), d_ok);
+                       (const uint8_t*)(d_in + ib), d_ok, (uint8_t*)nullptr);
     BCP_HIP_CHECK(hipGetLastError());
     BCP_HIP_CHECK(hipMemcpyAsync(h_ok, d_ok, n, hipMemcpyDeviceToHost, L.stream));
     BCP_HIP_CHECK(hipStreamSynchronize(L.stream));
@@ -247,7 +257,7 @@ static void enqueue_header_checks(hipStream_t stream, const unsigned char* d_in,
                        (uint32_t)C::N, (uint32_t)C::K, (int)n);
     BCP_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((bcpk::eh_verify<C>), dim3((unsigned)n), dim3(C::NTH), 0, stream,
-                       (const bcpk::EhBaseState*)d_states, (const uint8_t*)d_sols, d_status);
+                       (const bcpk::EhBaseState*)d_states, (const uint8_t*)d_sols, d_status, (uint8_t*)nullptr);
     BCP_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((bcpk::eh_header_check<P>), dim3((unsigned)n), dim3(64), 0, stream,
                        reinterpret_cast<const uint32_t*>(d_in), reinterpret_cast<const uint32_t*>(d_sols), d_lenok, limit,
@@ -380,6 +390,15 @@ void VerifyLane::Equihash(unsigned N, unsigned K, const EhBaseState* states,
     throw std::invalid_argument("EquihashVerifyBatch: unsupported (N,K)");
 }
 
+void VerifyLane::EquihashReasons(unsigned N, unsigned K, const EhBaseState* states,
+                                 const std::vector<unsigned char>* const* sols, size_t n, uint8_t* result, uint8_t* why) {
+    if (N == 200 && K == 9) return verify_lane<bcpk::EvCfg<200, 9>>(*impl, states, sols, n, result, why);
+    if (N == 96 && K == 5) return verify_lane<bcpk::EvCfg<96, 5>>(*impl, states, sols, n, result, why);
+    if (N == 48 && K == 5) return verify_lane<bcpk::EvCfg<48, 5>>(*impl, states, sols, n, result, why);
+    if (N == 96 && K == 3) return verify_lane<bcpk::EvCfg<96, 3>>(*impl, states, sols, n, result, why);
+    throw std::invalid_argument("EquihashVerifyReasons: unsupported (N,K)");
+}
+
 // One default (normal-priority) lane per device for the plain batch API.
 static VerifyLane& DefaultLane(int device, std::unique_lock<std::mutex>& hold) {
     static std::mutex m;
@@ -406,6 +425,19 @@ std::vector<uint8_t> EquihashVerifyBatch(unsigned n, unsigned k, const std::vect
     VerifyLane& lane = DefaultLane(device, hold);
     lane.Equihash(n, k, states.data(), ptrs.data(), states.size(), result.data());
     return result;
+}
+
+std::vector<uint8_t> EquihashVerifyReasons(unsigned n, unsigned k, const std::vector<EhBaseState>& states,
+                                           const std::vector<std::vector<unsigned char>>& solutions, int device) {
+    if (states.size() != solutions.size()) throw std::invalid_argument("states/solutions size mismatch");
+    std::vector<uint8_t> why(states.size(), 0), verdict(states.size(), 0);
+    if (states.empty()) return why;
+    std::vector<const std::vector<unsigned char>*> ptrs(solutions.size());
+    for (size_t i = 0; i < solutions.size(); ++i) ptrs[i] = &solutions[i];
+    std::unique_lock<std::mutex> hold;
+    VerifyLane& lane = DefaultLane(device, hold);
+    lane.EquihashReasons(n, k, states.data(), ptrs.data(), states.size(), verdict.data(), why.data());
+    return why;
 }
 
 void EquihashCheckHeadersBatch(unsigned n, unsigned k, const unsigned char* in140, const unsigned char* sols,

@@ -135,6 +135,22 @@ std::vector<uint8_t> EquihashVerifyBatch(unsigned n, unsigned k, const std::vect
                                          const std::vector<std::vector<unsigned char>>& solutions,
                                          int device = -1);
 
+// Which checks of the verifier kernel failed, one mask byte per item (diagnostics and tests; the
+// accepting paths only use the verdict). A solution of another length gets EH_WHY_LENGTH from
+// the host and nothing else: the kernel's bits for it are not reported.
+enum EhVerifyReason : uint8_t {
+    EH_WHY_COLLISION = 1, // some node's two children differ in the digit of the node's level
+    EH_WHY_ORDER = 2,     // some node's left first index is not below its right first index
+    EH_WHY_DUPLICATE = 4, // two positions hold the same index
+    EH_WHY_FINAL = 8,     // the root's last digit is not zero
+    EH_WHY_LENGTH = 16,   // the solution has another length
+};
+// Same lane, staging and kernel as EquihashVerifyBatch, the same four parameter sets; mask == 0
+// iff EquihashVerifyBatch accepts.
+std::vector<uint8_t> EquihashVerifyReasons(unsigned n, unsigned k, const std::vector<EhBaseState>& states,
+                                           const std::vector<std::vector<unsigned char>>& solutions,
+                                           int device = -1);
+
 // Block hashes of cnt headers given as (140-byte Equihash input, minimal solution) pairs:
 // hashes[32*i ..] = SHA256d(in140_i || compactsize || sol_i), pass[i] = 1 iff that hash, as a
 // 256-bit little-endian integer, is at or below the target. One workgroup per pair, the device
@@ -287,6 +303,9 @@ public:
     // wrong length is rejected.
     void Equihash(unsigned N, unsigned K, const EhBaseState* states, const std::vector<unsigned char>* const* sols,
                   size_t n, uint8_t* result);
+    // Equihash plus why[i] = EhVerifyReason bits of item i (EquihashVerifyReasons).
+    void EquihashReasons(unsigned N, unsigned K, const EhBaseState* states,
+                         const std::vector<unsigned char>* const* sols, size_t n, uint8_t* result, uint8_t* why);
     // Batches and items this lane has run (service statistics).
     uint64_t Batches() const;
     uint64_t Items() const;

@@ -359,6 +359,22 @@ void bind_gpu(pyb::module_& m) {
         },
         pyb::arg("n"), pyb::arg("k"), pyb::arg("states"), pyb::arg("solutions"), pyb::arg("device") = -1);
 
+    // which checks of eh_verify failed, one mask per solution (gpu_api.h EhVerifyReason)
+    m.def(
+        "eh_verify_reasons_gpu",
+        [](unsigned n, unsigned k, const std::vector<CBlake2b>& sts, const std::vector<pyb::bytes>& sols, int device) {
+            auto bs = states_from(sts);
+            std::vector<std::vector<unsigned char>> v;
+            for (auto& b : sols) v.push_back(to_vec(b));
+            std::vector<uint8_t> r;
+            {
+                pyb::gil_scoped_release rel;
+                r = gpu::EquihashVerifyReasons(n, k, bs, v, device);
+            }
+            return std::vector<int>(r.begin(), r.end());
+        },
+        pyb::arg("n"), pyb::arg("k"), pyb::arg("states"), pyb::arg("solutions"), pyb::arg("device") = -1);
+
     m.def(
         "sha256d_batch_gpu",
         [](const std::vector<pyb::bytes>& msgs, int device) {
