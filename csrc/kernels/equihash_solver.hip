@@ -18,7 +18,8 @@
 //    loads, straight into LDS): no run tables, slot maps or per-row gather maps.
 //  * Collisions on the remaining RB = DB-BB bits of the digit are found by a counting sort of
 //    the bucket on those bits and an atomic-free pair enumeration (scan + max-scan); each output
-//    row keeps a parent triple (producing bucket, LDS row i, LDS row j), so nothing ever carries
+//    row keeps a parent triple (producing bucket, LDS row i, LDS row j; in its slot or, see Memory
+//    layout, in the producing bucket's tables), so nothing ever carries
 //    index lists: the parents of a stage-s row are the stage-(s-1) slots bucket*AREA + i and
 //    bucket*AREA + j.
 //  * Depth-1 duplicate pruning (pairs whose rows share a parent are dropped) wherever the parent
@@ -37,12 +38,18 @@
 //    would not co-schedule separate generation and round kernels on a CU (profiles/equihash_r5.md);
 //    inside one workgroup the placement is given. profiles/equihash_r7.md has the measurements.
 //
-// Memory layout: every stage has its own slot array and a stage-s slot holds the row followed by
-// its parent word(s), so the emit writes one contiguous slot per output row and a pruning round
-// gets the parents with the rows. Keeping all K stage arrays costs ~50 words per slot per nonce
-// (≈17 GB per 32-nonce solver, against 288 GB of HBM); the parents must outlive the rows anyway
-// for the final expansion. Per row per round: one contiguous slot read, one slot write into a
-// claimed run.
+// Memory layout: every stage has its own slot array. Where the round that reads a stage prunes
+// (or the row has no room for the producing bucket), a stage-s slot holds the row followed by its
+// parent word(s), so the emit writes one contiguous slot per output row and the pruning round
+// gets the parents with the rows. The other stages ((200,9): 1-4, 6, 7) keep "table parents"
+// (EhCfg::tp, BCP_EH_TABLE_PARENTS): the slot is the row alone with the producing bucket d in its
+// padding, so rounds 2..K-1 do not fetch parent words they never use (they share the rows' cache
+// lines); the (j << 16 | i) word of every output row goes, in the emit's destination order, to a
+// per-bucket pair table (consecutive lanes store consecutive words) and the run bases of the
+// bucket to a run-base table, which only eh_expand reads. Keeping all K stage arrays and tables
+// costs ~50 words per slot per nonce (≈17 GB per 32-nonce solver, against 288 GB of HBM); the
+// parents must outlive the rows anyway for the final expansion. Per row per round: one contiguous
+// slot read, one slot write into a claimed run, one pair-table word.
 #include <hip/hip_runtime.h>
 
 #include "crypto/hashes.h"
@@ -85,11 +92,19 @@
 #ifndef BCP_EH_GW // (200,9) generation waves of a carrying round workgroup (the round keeps 1024 - 64*GW threads)
 #define BCP_EH_GW 4
 #endif
+#ifndef BCP_EH_TABLE_PARENTS // 1: stages read by a round that does not prune keep their parent words in per-bucket
+#define BCP_EH_TABLE_PARENTS 1 //    tables beside the slot array (EhCfg::tp); 0: every slot carries its parent word(s)
+#endif
 #ifndef BCP_EH_GROUPS_DEFAULT // nonce groups of a solver by its batch size (BCP_EH_GROUPS overrides at run time):
 #define BCP_EH_GROUPS_DEFAULT(batch) ((batch) >= 48 ? (batch) / 24 : 1) // groups of 24 nonces; measured at 96 (profiles/equihash_r7.md)
 #endif
 
 namespace bcpk {
+
+// (defined with the round kernels' geometry below; EhCfg's table-parent layout follows from them)
+template <class C> constexpr int round_nt(int stage, bool carry);
+template <class C> constexpr int round_mp(int stage, bool carry = false);
+template <class C> constexpr bool round_prunes(int stage, bool carry = false);
 
 // N, K: Equihash parameters. BB: bucket bits. CAP/CAP4/CAP3: LDS row capacity of rounds reading
 // rows of >= 5, 4, <= 3 words. NT: threads per round workgroup; WGCU: round workgroups per CU
@@ -151,9 +166,33 @@ struct EhCfg {
     static constexpr bool cp(int stage) {
         return stage >= 1 && stage < K && 32 * words(stage) - bits(stage) >= DR;
     }
-    static constexpr uint32_t rmask(int stage) { return cp(stage) ? RMASK : 0u; } // parent bits in a row's padding
-    // words per slot of stage s: the row, plus (s >= 1) its parent word(s)
-    static constexpr int sw(int stage) { return stage == 0 ? words(0) : words(stage) + (cp(stage) ? 1 : 2); }
+    // Table parents: a stage whose reading round does not prune (plain or carrying) and whose rows
+    // have BB padding bits keeps NO parent word in its slots. The whole producing bucket d rides
+    // in the row's padding, the (j << 16 | i) word of output ordinal t (the emit's destination
+    // order) goes to the pair table P[stage][nonce][d][t] (ptab() words per bucket, a coalesced
+    // store), and the run-base table B[stage][nonce][d][b] holds (claimed run start in area b) -
+    // (first ordinal of destination b), so a slot at position pos of area b has t = pos - B.
+    // Only eh_expand reads P and B: the rounds 2..K-1 that read such a stage fetch rows alone.
+    static constexpr int pad(int stage) { return 32 * words(stage) - bits(stage); }
+    static constexpr bool tp(int stage) {
+        return BCP_EH_TABLE_PARENTS && stage >= 1 && stage <= K - 2 && !round_prunes<EhCfg>(stage + 1) &&
+               !round_prunes<EhCfg>(stage + 1, true) && pad(stage) >= BB;
+    }
+    // pair-table words per producing bucket: every ordinal the emit of either variant can hold
+    static constexpr int ptab(int stage) {
+        const int a = round_mp<EhCfg>(stage, false) * round_nt<EhCfg>(stage, false);
+        const int b = GW_ > 0 ? round_mp<EhCfg>(stage, true) * round_nt<EhCfg>(stage, true) : 0;
+        return a > b ? a : b;
+    }
+    // eh_expand reads the producing bucket of a table stage through every padding bit (up to BB + 1):
+    // the rounds leave the bits above BB zero, so a set one marks a corrupt row
+    static constexpr uint32_t tpmask(int stage) { return (1u << (pad(stage) > BB ? BB + 1 : BB)) - 1; }
+    // parent bits in a row's padding
+    static constexpr uint32_t rmask(int stage) { return tp(stage) ? (uint32_t)NB - 1 : cp(stage) ? RMASK : 0u; }
+    // words per slot of stage s: the row, plus (s >= 1, no table parents) its parent word(s)
+    static constexpr int sw(int stage) {
+        return stage == 0 || tp(stage) ? words(stage) : words(stage) + (cp(stage) ? 1 : 2);
+    }
     static constexpr size_t ROWS = (size_t)NB * AREA; // slots per stage per nonce
     // 16-bit LDS histograms (two counters per word) where 32-bit ones would not fit two per CU
     static constexpr bool H16 = NB > 512;
@@ -577,7 +616,7 @@ template <class C> constexpr int un_walk_list(int cap) { return un_walk_bend<C>(
 // (the final round never carries: two of its workgroups share a CU and the generation tables
 // would not fit).
 template <class C> constexpr int round_nt(int stage, bool carry) { return carry && stage < C::K ? C::RNT : C::NT; }
-template <class C> constexpr int round_mp(int stage, bool carry = false) {
+template <class C> constexpr int round_mp(int stage, bool carry) {
     const int nt = round_nt<C>(stage, carry);
     return stage == C::K ? 1
                          : (C::AREA_NF + nt - 1) / nt + C::MPX +
@@ -602,7 +641,7 @@ template <class C> constexpr int round_lds(int stage, bool prune, bool carry = f
            (round_nt<C>(stage, carry) / 64 + 1) * 4 + gen;
 }
 // Depth-1 duplicate pruning wherever its parent words fit next to the full rows.
-template <class C> constexpr bool round_prunes(int stage, bool carry = false) {
+template <class C> constexpr bool round_prunes(int stage, bool carry) {
     // (the pruning start was measured on (200,9); the small configurations keep pruning from round 2)
     constexpr int from = C::K == 9 ? BCP_EH_PRUNE_FROM : 2;
     return (stage >= from || stage == C::K) && stage >= 2 && round_lds<C>(stage, true, carry) <= C::LDS_BUDGET;
@@ -831,7 +870,8 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 //   D3. one atomicAdd per destination bucket claims this bucket's runs there; counting sort of
 //       the pairs by destination;
 //   D4. one-lane-per-row emit (XOR, shift one digit, 16-byte stores) into the claimed runs,
-//       plus the parent word(s).
+//       plus the parent word(s), or (table parents) the bucket in the row's padding and the pair
+//       word into the bucket's pair table.
 // The final round (STAGE == K) sorts its one-word rows by key and lists the candidates: pairs
 // equal on all remaining bits.
 // Input rows whose slots carry compact parents keep the parent-bucket bits in their padding in
@@ -847,8 +887,9 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 template <class C, int STAGE, bool STAMP, bool CARRY = false>
 __global__ __launch_bounds__(C::NT) __attribute__((amdgpu_waves_per_eu(C::WGCU * C::NT / 256)))
 void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTRin, uint32_t* __restrict__ Rout,
-              uint32_t* __restrict__ CTRout, uint32_t* __restrict__ ncand, uint64_t* __restrict__ cand,
-              uint64_t* __restrict__ stamps, uint32_t* __restrict__ pdrop, int nbk, EhCarry carry) {
+              uint32_t* __restrict__ CTRout, uint32_t* __restrict__ Pout, uint32_t* __restrict__ Bout,
+              uint32_t* __restrict__ ncand, uint64_t* __restrict__ cand, uint64_t* __restrict__ stamps,
+              uint32_t* __restrict__ pdrop, int nbk, EhCarry carry) {
     constexpr int WI = C::words(STAGE - 1);
     constexpr int WO = (STAGE < C::K) ? C::words(STAGE) : 1;
     constexpr int CAP = C::cap(STAGE);                        // LDS rows / pair-list entries
@@ -864,6 +905,10 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     constexpr int MP = round_mp<C>(STAGE, CARRY);           // pairs per lane (registers)
     constexpr int SWI = C::sw(STAGE - 1);                  // words per input slot
     constexpr int SWO = STAGE < C::K ? C::sw(STAGE) : 1;   // words per output slot
+    constexpr bool TPO = !FINAL && C::tp(STAGE);           // output stage keeps its parents in tables (Pout, Bout)
+    constexpr int PTW = TPO ? C::ptab(STAGE) : 1;          // pair-table words per producing bucket
+    static_assert(!TPO || PTW >= MP * NT, "the pair table holds every ordinal this round's emit can have (the spair bound)");
+    static_assert(!(PRUNE && C::tp(STAGE - 1)), "a pruning round reads its parents from the slots");
     constexpr bool CPI = C::cp(STAGE - 1);                 // input slots carry one compact parent word
     constexpr uint32_t RMI = C::rmask(STAGE - 1);          // parent bits in the input rows' padding
     constexpr int SLI = (RPL + BCP_EH_PF_SLICES - 1) / BCP_EH_PF_SLICES; // prefetch slice (rows per phase)
@@ -1002,8 +1047,15 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         // loads followed by MP emit store groups, so the commit waits for its loads only.
         const auto rs_out = buf_rsrc(Rout, 0);
         const uint32_t z[SWO] = {};
+        if constexpr (TPO) { // D3's run-base stores come between the last prefetch slice and the emit
 #pragma unroll
-        for (int u = 0; u < MP; ++u) row_store<SWO>(rs_out, OOB + 256 * u, z); // distinct offsets: identical stores would be merged
+            for (int k = 0; k < BPT; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, rs_out, OOB + 256 * MP + 64 * k, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < MP; ++u) {
+            row_store<SWO>(rs_out, OOB + 256 * u, z); // distinct offsets: identical stores would be merged
+            if constexpr (TPO) __builtin_amdgcn_raw_buffer_store_b32(0u, rs_out, OOB + 256 * u + 128, 0, 0); // the unit's pair-table store
+        }
     }
     if constexpr (FOLD) {
         for (int k = tid; k < C::NRESTS; k += NT) bend[k] = 0;
@@ -1199,9 +1251,14 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
 #pragma unroll
             for (int k = 0; k < BPT; ++k) { // LDS slot t of destination b -> run position base[b] + t
                 const int b = tid * BPT + k;
+                const uint32_t rb = myb[k] - start;
                 if (b < C::NB) {
-                    base[b] = (HT)(myb[k] - start);
+                    base[b] = (HT)rb;
                     start += hget(hist_, b);
+                }
+                if constexpr (TPO) { // the run base of (d, b) for eh_expand: consecutive lanes, consecutive words
+                    const auto rs_b = buf_rsrc(Bout + ((size_t)nonce * C::NB + d) * C::NB, C::NB * 4);
+                    __builtin_amdgcn_raw_buffer_store_b32(rb, rs_b, b < C::NB ? (uint32_t)b * 4 : OOB, 0, 0);
                 }
             }
             eh_bar<9>();
@@ -1211,6 +1268,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             constexpr uint32_t OCAP = C::cap(STAGE + 1 <= C::K ? STAGE + 1 : C::K);
             constexpr uint32_t RMO = C::rmask(STAGE);
             const auto rs_out = buf_rsrc(Rout + (size_t)nonce * C::ROWS * SWO, (uint32_t)(C::ROWS * SWO * 4));
+            const auto rs_p = buf_rsrc(Pout + (TPO ? ((size_t)nonce * C::NB + d) * PTW : 0), TPO ? PTW * 4 : 0);
 #pragma unroll
             for (int u = 0; u < MP; ++u) { // fixed trip count, unconditional stores (see issue())
                 const uint32_t t = tid + u * NT;
@@ -1229,7 +1287,9 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                 uint32_t ov[SWO] = {};
 #pragma unroll
                 for (int w = 0; w < WO; ++w) ov[w] = o[w];
-                if constexpr (C::cp(STAGE)) {
+                if constexpr (TPO) {
+                    ov[WO - 1] |= (uint32_t)d & RMO; // (d < NB: the whole bucket)
+                } else if constexpr (C::cp(STAGE)) {
                     ov[WO - 1] |= (d >> C::DX) & RMO;
                     ov[WO] = cpack<C>(d, i, j);
                 } else {
@@ -1237,6 +1297,8 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     ov[WO + 1] = d;
                 }
                 row_store<SWO>(rs_out, ok ? slot * (SWO * 4) : OOB, ov);
+                // table parents: the pair word of ordinal t, lane after lane (t < MP * NT <= PTW)
+                if constexpr (TPO) __builtin_amdgcn_raw_buffer_store_b32(pr, rs_p, t < np ? t * 4 : OOB, 0, 0);
             }
         }
         eh_bar<EH_NBAR>();
@@ -1253,8 +1315,11 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
 // ------------------------------------------------------------------ tree expansion
 // The stage arrays (stage-s slot = row, parent word(s)) passed by value; LEAF: stage-0 leaf
 // index per slot.
+// p, b: the pair and run-base tables of the stages with table parents (EhCfg::tp).
 struct EhStages {
     const uint32_t* r[16];
+    const uint32_t* p[16];
+    const uint32_t* b[16];
 };
 template <class C>
 __global__ __launch_bounds__(C::L < 64 ? 64 : C::L) void eh_expand(const uint32_t* __restrict__ LEAF, EhStages st,
@@ -1295,7 +1360,19 @@ __global__ __launch_bounds__(C::L < 64 ? 64 : C::L) void eh_expand(const uint32_
         __syncthreads();
         if (s > 1 && t < 2 * cnt) { // stage s-1 slot: row words, then the parent word(s)
             const uint32_t* q = st.r[s - 1] + ((size_t)nonce * C::ROWS + buf[cur][t]) * C::sw(s - 1) + C::words(s - 1);
-            if (C::cp(s - 1))
+            if (C::tp(s - 1)) {
+                // table parents, three dependent reads: d from the row's padding, the slot's
+                // ordinal in d's emit from the run base of (d, area), the pair word of that
+                // ordinal. A d or an ordinal outside its table is clamped to entry 0 and the
+                // candidate rejected; i and j are checked as LDS rows at the next level.
+                const uint32_t area = buf[cur][t] / C::AREA, pos = buf[cur][t] % C::AREA;
+                uint32_t d = q[-1] & C::tpmask(s - 1);
+                if (d >= (uint32_t)C::NB) d = 0, dup = 1;
+                const size_t db = (size_t)nonce * C::NB + d;
+                uint32_t o = pos - st.b[s - 1][db * C::NB + area];
+                if (o >= (uint32_t)C::ptab(s - 1)) o = 0, dup = 1;
+                tri[t] = ((uint64_t)d << 32) | st.p[s - 1][db * C::ptab(s - 1) + o];
+            } else if (C::cp(s - 1))
                 tri[t] = ((uint64_t)cunpack_d<C>(q[0], q[-1]) << 32) | (q[0] & C::IMASK);
             else
                 tri[t] = ((uint64_t)q[1] << 32) | q[0];
@@ -1396,6 +1473,10 @@ struct EquihashGpuSolver::Impl {
     DevBuf<uint32_t> d_ctr, d_leaf, d_ncand, d_idx, d_valid, d_pdrop, d_nout, d_out;
     DevBuf<uint64_t> d_cand;
     DevBuf<uint32_t> d_rst[16]; // merged layout: stage-s slot arrays (s = 0..K-1)
+    DevBuf<uint32_t> d_ptab[16], d_btab[16]; // stages with table parents: pair tables [nonce][d][ptab], run bases [nonce][d][b]
+    std::vector<bool> table;                 // per stage: table parents
+    std::vector<size_t> ptab_words;          // per stage: pair-table words per producing bucket
+    std::vector<uint32_t> tp_mask;           // per stage: padding bits eh_expand reads the producing bucket through
     HostBuf<bcpk::EhBaseState> h_states;
     HostBuf<uint32_t> h_ncand, h_idx, h_ctr0, h_ctr_all, h_pdrop, h_nout, h_out;
     size_t outq = 0; // compact-list entries copied back with every batch (more: a second copy)
@@ -1435,11 +1516,24 @@ struct EquihashGpuSolver::Impl {
             compact.push_back(C::cp(st));
             row_words.push_back(C::words(st));
         }
+        table.clear();
+        ptab_words.clear();
+        tp_mask.clear();
+        for (int st = 0; st < C::K; ++st) {
+            table.push_back(C::tp(st));
+            ptab_words.push_back(C::tp(st) ? C::ptab(st) : 0);
+            tp_mask.push_back(C::tp(st) ? C::tpmask(st) : 0u);
+        }
         kstages = C::K;
         d_states.alloc(batch);
         h_states.alloc(batch);
         static_assert(C::K <= 16, "stage arrays");
         for (int s = 0; s < C::K; ++s) d_rst[s].alloc((size_t)batch * C::ROWS * C::sw(s));
+        for (int s = 0; s < C::K; ++s)
+            if (C::tp(s)) {
+                d_ptab[s].alloc((size_t)batch * C::NB * C::ptab(s));
+                d_btab[s].alloc((size_t)batch * C::NB * C::NB);
+            }
         d_ctr.alloc((size_t)C::K * batch * C::NB);
         d_leaf.alloc((size_t)batch * C::ROWS);
         cp_ib = C::IB, cp_dh = C::DH, cp_dhm = C::DHM, cp_dx = C::DX, cp_rmask = C::RMASK, cp_imask = C::IMASK;
@@ -1460,7 +1554,7 @@ struct EquihashGpuSolver::Impl {
         h_ctr_all.alloc((size_t)C::K * batch * C::NB);
         d_stamps.alloc((size_t)C::K * batch * C::NB * 16);
         bytes = d_leaf.n * 4 + d_ctr.n * 4 + d_idx.n * 4;
-        for (int s = 0; s < C::K; ++s) bytes += d_rst[s].n * 4;
+        for (int s = 0; s < C::K; ++s) bytes += (d_rst[s].n + d_ptab[s].n + d_btab[s].n) * 4;
     }
 
     // Persistent round kernels: as many workgroups as fit on the device at once.
@@ -1482,6 +1576,9 @@ struct EquihashGpuSolver::Impl {
         uint32_t* rout = S < C::K ? d_rst[S].p + o * C::ROWS * C::sw(S < C::K ? S : 0) : nullptr;
         const uint32_t* cin = d_ctr.p + ((size_t)(S - 1) * batch + o) * C::NB;
         uint32_t* cout = S < C::K ? d_ctr.p + ((size_t)S * batch + o) * C::NB : nullptr;
+        constexpr bool TP = S < C::K && C::tp(S < C::K ? S : 0); // the output stage's parent tables
+        uint32_t* pout = TP ? d_ptab[S < C::K ? S : 0].p + o * C::NB * C::ptab(S < C::K ? S : 0) : nullptr;
+        uint32_t* bout = TP ? d_btab[S < C::K ? S : 0].p + o * C::NB * C::NB : nullptr;
         uint32_t* nc = d_ncand.p + o;
         uint64_t* cd = d_cand.p + o * C::MAXCAND;
         const int nbk = C::NB * gn;
@@ -1495,7 +1592,7 @@ struct EquihashGpuSolver::Impl {
                 cy.CTR0 = d_ctr.p + p * C::NB;
                 cy.nonces = next;
                 hipLaunchKernelGGL((bcpk::eh_round<C, S, false, true>), dim3(round_grid<C, S, false, true>(nbk)),
-                                   dim3(C::NT), 0, stream, rin, cin, rout, cout, nc, cd, nullptr,
+                                   dim3(C::NT), 0, stream, rin, cin, rout, cout, pout, bout, nc, cd, nullptr,
                                    d_pdrop.p + o * PDW, nbk, cy);
                 ++stats.carry_launches;
                 return;
@@ -1504,14 +1601,22 @@ struct EquihashGpuSolver::Impl {
         if (stamp_mode) {
             uint64_t* st = d_stamps.p + ((size_t)(S - 1) * batch + o) * C::NB * 16;
             hipLaunchKernelGGL((bcpk::eh_round<C, S, true>), dim3(round_grid<C, S, true, false>(nbk)), dim3(C::NT), 0,
-                               stream, rin, cin, rout, cout, nc, cd, st, d_pdrop.p + o * PDW, nbk, cy);
+                               stream, rin, cin, rout, cout, pout, bout, nc, cd, st, d_pdrop.p + o * PDW, nbk, cy);
         } else {
             hipLaunchKernelGGL((bcpk::eh_round<C, S, false>), dim3(round_grid<C, S, false, false>(nbk)), dim3(C::NT), 0,
-                               stream, rin, cin, rout, cout, nc, cd, nullptr, d_pdrop.p + o * PDW, nbk, cy);
+                               stream, rin, cin, rout, cout, pout, bout, nc, cd, nullptr, d_pdrop.p + o * PDW, nbk,
+                               cy);
         }
     }
     template <class C, int... S> void launch_rounds(int noff, int gn, int next, std::integer_sequence<int, S...>) {
         (launch_round<C, S + 1>(noff, gn, next), ...);
+    }
+
+    // what eh_expand walks: the slot arrays and, for the stages with table parents, their tables
+    template <class C> bcpk::EhStages stage_ptrs() const {
+        bcpk::EhStages st{};
+        for (int s = 0; s < C::K; ++s) st.r[s] = d_rst[s].p, st.p[s] = d_ptab[s].p, st.b[s] = d_btab[s].p;
+        return st;
     }
 
     template <class C> void alloc_pow() {
@@ -1541,6 +1646,10 @@ struct EquihashGpuSolver::Impl {
             if (d_leaf.n) BCP_HIP_CHECK(hipMemsetAsync(d_leaf.p, 0xff, d_leaf.n * sizeof(uint32_t), stream));
             for (int s = 0; s < C::K; ++s)
                 if (d_rst[s].n) BCP_HIP_CHECK(hipMemsetAsync(d_rst[s].p, 0xff, d_rst[s].n * sizeof(uint32_t), stream));
+            for (int s = 0; s < C::K; ++s) {
+                if (d_ptab[s].n) BCP_HIP_CHECK(hipMemsetAsync(d_ptab[s].p, 0xff, d_ptab[s].n * sizeof(uint32_t), stream));
+                if (d_btab[s].n) BCP_HIP_CHECK(hipMemsetAsync(d_btab[s].p, 0xff, d_btab[s].n * sizeof(uint32_t), stream));
+            }
         }
         BCP_HIP_CHECK(hipEventRecord(ev0, stream));
         // header-shaped inputs (140 B: g lands at byte 12 of the final block) take the
@@ -1589,8 +1698,7 @@ struct EquihashGpuSolver::Impl {
             launch_rounds<C>(noff, gn, next, std::make_integer_sequence<int, C::K>{});
         }
         constexpr int EB = C::L < 64 ? 64 : C::L;
-        bcpk::EhStages stages{};
-        for (int s = 0; s < C::K; ++s) stages.r[s] = d_rst[s].p;
+        const bcpk::EhStages stages = stage_ptrs<C>();
         hipLaunchKernelGGL((bcpk::eh_expand<C>), dim3(C::MAXCAND * nstates), dim3(EB), 0, stream, d_leaf.p, stages,
                            d_ncand.p, d_cand.p, d_idx.p, d_valid.p, d_nout.p, d_out.p);
         BCP_HIP_CHECK(hipEventRecord(ev_rounds, stream));
@@ -1730,7 +1838,7 @@ std::vector<uint64_t> EquihashGpuSolver::DebugDump(int nonce) {
     std::vector<uint32_t> leaf(R);
     BCP_HIP_CHECK(hipMemcpy(leaf.data(), m.d_leaf.p + (size_t)nonce * R, R * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < R; ++i) out[i] = leaf[i];
-    // the parent word(s) follow the row in every stage-s slot of nonce 0 (bcpk::cpack layout)
+    // the parent word(s) follow the row in every stage-s slot without table parents (bcpk::cpack layout)
     auto cunpack_d = [&](uint32_t pw, uint32_t last) {
         return ((pw >> m.cp_ib) & m.cp_dhm) | (((pw >> (16 + m.cp_ib)) & m.cp_dhm) << m.cp_dh) |
                ((last & m.cp_rmask) << m.cp_dx);
@@ -1739,6 +1847,27 @@ std::vector<uint64_t> EquihashGpuSolver::DebugDump(int nonce) {
         const size_t sw = m.slot_words[s], w = m.row_words[s];
         std::vector<uint32_t> buf(R * sw);
         BCP_HIP_CHECK(hipMemcpy(buf.data(), m.d_rst[s].p + (size_t)nonce * R * sw, R * sw * 4, hipMemcpyDeviceToHost));
+        if (m.table[s]) {
+            // table parents: the triple through the run-base and pair tables, as eh_expand walks it;
+            // a slot never written keeps the SetDebug fill in every row word (a row ends in zero
+            // padding above its producing bucket, or is not all-ones with overwhelming odds)
+            const size_t NB = m.nb, area = R / NB, pw = m.ptab_words[s];
+            std::vector<uint32_t> bt(NB * NB), pt(NB * pw);
+            BCP_HIP_CHECK(hipMemcpy(bt.data(), m.d_btab[s].p + (size_t)nonce * NB * NB, bt.size() * 4, hipMemcpyDeviceToHost));
+            BCP_HIP_CHECK(hipMemcpy(pt.data(), m.d_ptab[s].p + (size_t)nonce * NB * pw, pt.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < R; ++i) {
+                const uint32_t* row = &buf[i * sw];
+                bool unwritten = true;
+                for (size_t x = 0; x < w; ++x) unwritten &= row[x] == 0xffffffffu;
+                const uint32_t d = row[w - 1] & m.tp_mask[s];
+                const uint32_t t = d < NB ? (uint32_t)(i % area) - bt[d * NB + i / area] : 0u;
+                if (unwritten)
+                    out[s * R + i] = ~0ull;
+                else // (a bucket or an ordinal outside its table reads as i = j = 0xffff: no LDS row)
+                    out[s * R + i] = ((uint64_t)d << 32) | (d < NB && t < pw ? pt[d * pw + t] : 0xffffffffu);
+            }
+            continue;
+        }
         for (size_t i = 0; i < R; ++i) {
             const uint32_t* q = &buf[i * sw + w];
             if (m.compact[s] && q[0] == 0xffffffffu) // never written (SetDebug fill): no LDS row index is all-ones
@@ -1765,7 +1894,35 @@ std::vector<uint32_t> EquihashGpuSolver::DebugExpandCorrupt(int mode) {
     const size_t st = m.kstages - 1; // the stage the final round read
     const uint32_t d = (uint32_t)(tri >> 32), i = (uint32_t)tri & 0xffff;
     uint32_t* slot = m.d_rst[st].p + ((size_t)d * (m.rows / m.nb) + i) * m.slot_words[st] + m.row_words[st];
-    if (mode != 0) {
+    if (mode == 3 || mode == 4) {
+        // The table walk of a stage-(K-2) parent of the first candidate: mode 3 sets a padding bit
+        // above the producing bucket in its row (a bucket >= NB), mode 4 rewrites the run base of
+        // its (bucket, area) so that the slot's ordinal is the first one past the pair table.
+        if (st < 2 || !m.table[st - 1] || m.tp_mask[st - 1] < m.nb)
+            throw std::invalid_argument("DebugExpandCorrupt: modes 3 and 4 need table parents with spare padding in stage K-2");
+        uint32_t w[2] = {0, 0}; // the stage-(K-1) slot's parent word(s) -> its left parent (area d1, position i1)
+        BCP_HIP_CHECK(hipMemcpy(w, slot, m.compact[st] ? 4 : 8, hipMemcpyDeviceToHost));
+        uint32_t last = 0;
+        if (m.compact[st]) BCP_HIP_CHECK(hipMemcpy(&last, slot - 1, 4, hipMemcpyDeviceToHost));
+        const uint32_t d1 = m.compact[st] ? ((w[0] >> m.cp_ib) & m.cp_dhm) | (((w[0] >> (16 + m.cp_ib)) & m.cp_dhm) << m.cp_dh) |
+                                                ((last & m.cp_rmask) << m.cp_dx)
+                                          : w[1];
+        const uint32_t i1 = (m.compact[st] ? w[0] & m.cp_imask : w[0]) & 0xffff;
+        const size_t area = m.rows / m.nb;
+        if (d1 >= m.nb || i1 >= area) throw std::runtime_error("DebugExpandCorrupt: the first candidate's parent is out of range");
+        uint32_t* lw = m.d_rst[st - 1].p + ((size_t)d1 * area + i1) * m.slot_words[st - 1] + m.row_words[st - 1] - 1;
+        uint32_t x = 0;
+        BCP_HIP_CHECK(hipMemcpy(&x, lw, 4, hipMemcpyDeviceToHost));
+        if (mode == 3) {
+            x |= (uint32_t)m.nb;
+            BCP_HIP_CHECK(hipMemcpy(lw, &x, 4, hipMemcpyHostToDevice));
+        } else {
+            const uint32_t d2 = x & m.tp_mask[st - 1];
+            if (d2 >= m.nb) throw std::runtime_error("DebugExpandCorrupt: the parent row's bucket is out of range");
+            const uint32_t rb = i1 - (uint32_t)m.ptab_words[st - 1];
+            BCP_HIP_CHECK(hipMemcpy(m.d_btab[st - 1].p + (size_t)d2 * m.nb + d1, &rb, 4, hipMemcpyHostToDevice));
+        }
+    } else if (mode != 0) {
         if (m.compact[st]) {
             // compact word: i | j << 16 with the bucket's bits in the spare high bits of each half
             uint32_t w = 0;
@@ -1784,8 +1941,7 @@ std::vector<uint32_t> EquihashGpuSolver::DebugExpandCorrupt(int mode) {
     dispatch_cfg(m.n, m.k, [&](auto c) {
         using C = decltype(c);
         constexpr int EB = C::L < 64 ? 64 : C::L;
-        bcpk::EhStages stages{};
-        for (int s2 = 0; s2 < C::K; ++s2) stages.r[s2] = m.d_rst[s2].p;
+        const bcpk::EhStages stages = m.stage_ptrs<C>();
         hipLaunchKernelGGL((bcpk::eh_expand<C>), dim3(C::MAXCAND), dim3(EB), 0, m.stream, m.d_leaf.p, stages,
                            m.d_ncand.p, m.d_cand.p, m.d_idx.p, m.d_valid.p, m.d_nout.p, m.d_out.p);
     });

@@ -118,8 +118,11 @@ public:
     std::vector<uint32_t> DebugFills(int nonce);    // debug mode: the nonce's bucket fill counters, K stages x NB
     // Test hook (after a Solve): re-run the tree expansion of nonce 0's candidates with the first
     // candidate's left stage-(K-1) parent corrupted - mode 1: bucket out of range, mode 2: LDS
-    // row out of range, 0: untouched. Returns each candidate's valid flag; the expansion must
-    // reject the corrupted candidate without touching memory outside the stage arrays.
+    // row out of range, 0: untouched. Modes 3 and 4 corrupt the table walk of that slot's left
+    // stage-(K-2) parent (a stage with table parents, else they throw) - 3: producing bucket out of
+    // range in the row's padding, 4: a run base that puts the slot's ordinal past its pair table.
+    // Returns each candidate's valid flag; the expansion must reject the corrupted candidate
+    // without touching memory outside the stage arrays and tables.
     std::vector<uint32_t> DebugExpandCorrupt(int mode);
     std::vector<std::vector<double>> PhaseCycles(int nonces);
     void ResetStats();
