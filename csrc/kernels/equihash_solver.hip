@@ -37,23 +37,12 @@
 //    barriers, the same number on either path; nothing waits across workgroups. The dispatcher
 //    would not co-schedule separate generation and round kernels on a CU (profiles/equihash_r5.md);
 //    inside one workgroup the placement is given. profiles/equihash_r7.md has the measurements.
-//
-// Memory layout: every stage has its own slot array. Where the round that reads a stage prunes
-// (or the row has no room for the producing bucket), a stage-s slot holds the row followed by its
-// parent word(s), so the emit writes one contiguous slot per output row and the pruning round
-// gets the parents with the rows. The other stages ((200,9): 1-4, 6, 7) keep "table parents"
-// (EhCfg::tp, BCP_EH_TABLE_PARENTS): the slot is the row alone with the producing bucket d in its
-// padding, so rounds 2..K-1 do not fetch parent words they never use (they share the rows' cache
-// lines); the (j << 16 | i) word of every output row goes, in the emit's destination order, to a
-// per-bucket pair table (consecutive lanes store consecutive words) and the run bases of the
-// bucket to a run-base table, which only eh_expand reads. Keeping all K stage arrays and tables
-// costs ~50 words per slot per nonce (≈17 GB per 32-nonce solver, against 288 GB of HBM); the
-// parents must outlive the rows anyway for the final expansion. Per row per round: one contiguous
-// slot read, one slot write into a claimed run, one pair-table word.
+// Memory layout and kernel geometry: equihash_layout.h (checked on the CPU by csrc/test/equihash_layout_tests.cpp).
 #include <hip/hip_runtime.h>
 
 #include "crypto/hashes.h"
 #include "kernels/blake2b_device.h"
+#include "kernels/equihash_layout.h"
 #include "kernels/equihash_pow.h"
 #include "kernels/gpu_api.h"
 #include "kernels/hip_util.h"
@@ -66,34 +55,12 @@
 
 // Build options (each either the measured default or covered by the GPU tests; the variants that
 // were measured and rejected in rounds 3-5 are at git tag solver-r5-knobs, profiles/equihash_r4.md
-// and profiles/equihash_r5.md):
+// and profiles/equihash_r5.md; the options that shape the layout are in equihash_layout.h):
 #ifndef BCP_EH_XCD_MAP // 1: every kernel of a nonce runs on one XCD (nonce % 8), so the run writes
 #define BCP_EH_XCD_MAP 1  //    of a nonce meet in one L2 (batches that are a multiple of 8 nonces)
 #endif
 #ifndef BCP_EH_PF_SLICES // the next bucket's rows are prefetched in this many slices
 #define BCP_EH_PF_SLICES 3
-#endif
-#ifndef BCP_EH_GEN_HPT // (200,9) register generation: hashes per thread
-#define BCP_EH_GEN_HPT 2
-#endif
-#ifndef BCP_EH_GEN_NT // (200,9) register generation: threads per workgroup
-#define BCP_EH_GEN_NT 512
-#endif
-#ifndef BCP_EH_PRUNE_FROM // first round that drops pairs sharing a parent (reads the parent words with the rows);
-                          // the final round always does.
-#define BCP_EH_PRUNE_FROM 9 //  9 = the final round only: +4.2% Sol/s over 2 at the same recall (profiles/equihash_r5.md)
-#endif
-#ifndef BCP_EH_MP_LATE // extra pair slots per lane in the late collision rounds (see round_mp)
-#define BCP_EH_MP_LATE 1
-#endif
-#ifndef BCP_EH_MP_LATE_FROM
-#define BCP_EH_MP_LATE_FROM 8
-#endif
-#ifndef BCP_EH_GW // (200,9) generation waves of a carrying round workgroup (the round keeps 1024 - 64*GW threads)
-#define BCP_EH_GW 4
-#endif
-#ifndef BCP_EH_TABLE_PARENTS // 1: stages read by a round that does not prune keep their parent words in per-bucket
-#define BCP_EH_TABLE_PARENTS 1 //    tables beside the slot array (EhCfg::tp); 0: every slot carries its parent word(s)
 #endif
 #ifndef BCP_EH_GROUPS_DEFAULT // nonce groups of a solver by its batch size (BCP_EH_GROUPS overrides at run time):
 #define BCP_EH_GROUPS_DEFAULT(batch) ((batch) >= 48 ? (batch) / 24 : 1) // groups of 24 nonces; measured at 96 (profiles/equihash_r7.md)
@@ -101,125 +68,6 @@
 
 namespace bcpk {
 
-// (defined with the round kernels' geometry below; EhCfg's table-parent layout follows from them)
-template <class C> constexpr int round_nt(int stage, bool carry);
-template <class C> constexpr int round_mp(int stage, bool carry = false);
-template <class C> constexpr bool round_prunes(int stage, bool carry = false);
-
-// N, K: Equihash parameters. BB: bucket bits. CAP/CAP4/CAP3: LDS row capacity of rounds reading
-// rows of >= 5, 4, <= 3 words. NT: threads per round workgroup; WGCU: round workgroups per CU
-// the LDS budget must allow. GENWG/NTG: LDS-sorted generation geometry; GNT x GHPT: register
-// generation (threads x hashes per thread; 0 = use the LDS-sorted kernel).
-template <int N_, int K_, int BB_, int CAP_, int NT_, int GENWG_, int NTG_, int MAXCAND_, int CAP4_ = CAP_,
-          int CAP3_ = CAP_, int WGCU_ = 1, int GNT_ = 512, int GHPT_ = 2, int CAPF_ = 0, int MPX_ = 0, int GW_ = 0>
-struct EhCfg {
-    static constexpr int N = N_, K = K_;
-    static constexpr int DB = N / (K + 1);           // digit bits
-    static constexpr int BB = BB_;                   // bucket bits
-    static constexpr int RB = DB - BB_;              // in-bucket collision bits
-    static constexpr int NB = 1 << BB_;              // buckets (= areas of every stage)
-    static constexpr int NRESTS = 1 << RB;
-    // LDS row capacity of a round by the width of the rows it reads: the narrow late rounds
-    // hold more rows (their buckets and pair lists overflow most, from duplicate subtrees)
-    static constexpr int CAP = CAP_;                 // rounds reading >= 5-word rows
-    // CAPF: the final round's capacity (0 = CAP3). Without depth-1 pruning before the final round,
-    // duplicate subtrees pile up in a few stage-(K-1) buckets; a larger final area keeps the valid
-    // rows of such a bucket from being crowded out (which rows are dropped follows the atomics).
-    static constexpr int CAPF = CAPF_ > 0 ? CAPF_ : CAP3_;
-    static constexpr int MPX = MPX_;                 // extra pair-list slots per lane in every collision round
-    static constexpr int cap(int round) {
-        return round == K_ ? CAPF : words(round - 1) >= 5 ? CAP_ : words(round - 1) == 4 ? CAP4_ : CAP3_;
-    }
-    // largest non-final capacity (sizes the per-lane pair registers) and the area of every stage
-    static constexpr int AREA_NF = CAP_ > CAP4_ ? (CAP_ > CAP3_ ? CAP_ : CAP3_) : (CAP4_ > CAP3_ ? CAP4_ : CAP3_);
-    static constexpr int AREA = AREA_NF > CAPF ? AREA_NF : CAPF;
-    static constexpr int NT = NT_;                   // threads per round workgroup
-    static constexpr int NW = NT_ / 64;
-    // GW: generation waves a carrying collision round (eh_round with CARRY) runs beside its
-    // NT - 64*GW round threads; 0 = the configuration never carries generation
-    static constexpr int GW = GW_;
-    static constexpr int RNT = NT_ - 64 * GW_;       // round threads of a carrying round
-    static constexpr int WGCU = WGCU_;
-    static constexpr int LDS_BUDGET = 160 * 1024 / WGCU_;
-    static constexpr int INIT = 1 << (DB + 1);
-    static constexpr int GENWG = GENWG_;             // LDS-sorted generation: workgroups per nonce
-    static constexpr int NTG = NTG_;                 // LDS-sorted generation: threads per workgroup
-    static constexpr int GNT = GNT_, GHPT = GHPT_;   // register generation geometry
-    static constexpr int RPW = INIT / GENWG_;        // rows per generation workgroup
-    static constexpr int IPH = 512 / N;
-    static constexpr int NBYTES = N / 8;
-    static constexpr int MAXCAND = MAXCAND_;
-    static constexpr int L = 1 << K;
-    static constexpr int bits(int stage) { return N - stage * DB - BB_; }
-    static constexpr int words(int stage) { return (bits(stage) + 31) / 32; }
-    static constexpr int WMAX = words(0);
-    // Compact parents: the triple (d, i, j) as ONE word. i and j take IB bits each in the two
-    // halves of the word, the 16 - IB spare bits of each half carry DX bits of d, and the DR
-    // remaining bits of d ride in the low (padding) bits of the row's last word.
-    static constexpr int IB = AREA <= 4096 ? 12 : 13;
-    static constexpr int DH = 16 - IB;
-    static constexpr uint32_t DHM = (1u << DH) - 1;
-    static constexpr int DX = 2 * DH;
-    static constexpr int DR = BB_ > DX ? BB_ - DX : 0;
-    static constexpr uint32_t RMASK = (1u << DR) - 1;
-    static constexpr uint32_t IMASK = ((1u << IB) - 1) * 0x10001u;
-    static constexpr bool cp(int stage) {
-        return stage >= 1 && stage < K && 32 * words(stage) - bits(stage) >= DR;
-    }
-    // Table parents: a stage whose reading round does not prune (plain or carrying) and whose rows
-    // have BB padding bits keeps NO parent word in its slots. The whole producing bucket d rides
-    // in the row's padding, the (j << 16 | i) word of output ordinal t (the emit's destination
-    // order) goes to the pair table P[stage][nonce][d][t] (ptab() words per bucket, a coalesced
-    // store), and the run-base table B[stage][nonce][d][b] holds (claimed run start in area b) -
-    // (first ordinal of destination b), so a slot at position pos of area b has t = pos - B.
-    // Only eh_expand reads P and B: the rounds 2..K-1 that read such a stage fetch rows alone.
-    static constexpr int pad(int stage) { return 32 * words(stage) - bits(stage); }
-    static constexpr bool tp(int stage) {
-        return BCP_EH_TABLE_PARENTS && stage >= 1 && stage <= K - 2 && !round_prunes<EhCfg>(stage + 1) &&
-               !round_prunes<EhCfg>(stage + 1, true) && pad(stage) >= BB;
-    }
-    // pair-table words per producing bucket: every ordinal the emit of either variant can hold
-    static constexpr int ptab(int stage) {
-        const int a = round_mp<EhCfg>(stage, false) * round_nt<EhCfg>(stage, false);
-        const int b = GW_ > 0 ? round_mp<EhCfg>(stage, true) * round_nt<EhCfg>(stage, true) : 0;
-        return a > b ? a : b;
-    }
-    // eh_expand reads the producing bucket of a table stage through every padding bit (up to BB + 1):
-    // the rounds leave the bits above BB zero, so a set one marks a corrupt row
-    static constexpr uint32_t tpmask(int stage) { return (1u << (pad(stage) > BB ? BB + 1 : BB)) - 1; }
-    // parent bits in a row's padding
-    static constexpr uint32_t rmask(int stage) { return tp(stage) ? (uint32_t)NB - 1 : cp(stage) ? RMASK : 0u; }
-    // words per slot of stage s: the row, plus (s >= 1, no table parents) its parent word(s)
-    static constexpr int sw(int stage) {
-        return stage == 0 || tp(stage) ? words(stage) : words(stage) + (cp(stage) ? 1 : 2);
-    }
-    static constexpr size_t ROWS = (size_t)NB * AREA; // slots per stage per nonce
-    // 16-bit LDS histograms (two counters per word) where 32-bit ones would not fit two per CU
-    static constexpr bool H16 = NB > 512;
-    static constexpr int HW = H16 ? NB / 2 : NB;      // words per histogram
-    static_assert(RPW * GENWG_ == INIT && RPW < 65535, "generation split");
-    static_assert(RB > 0 && DB < 32, "digit geometry");
-    static_assert(AREA < (1 << IB), "LDS row indices in parent words and signatures");
-    static_assert(NT_ % 64 == 0 && NT_ <= 1024 && (NB <= NT_ || NB % NT_ == 0) && NB <= NTG_ && NT_ / 64 <= 64,
-                  "workgroup shape");
-    static_assert(words(K - 1) == 1, "final round keeps whole rows in one LDS word");
-    static_assert(GW_ == 0 || (WGCU_ == 1 && RNT >= 128 && (NB <= RNT || NB % RNT == 0)), "carrying workgroup shape");
-};
-
-// Mainnet/testnet (200,9): 512 buckets x ~4096 rows, one 1024-thread round workgroup per CU;
-// (96,5); regtest (48,5).
-#ifndef BCP_EH_CAPF // (200,9) final-round capacity (rows per bucket; the stage areas grow to match)
-#define BCP_EH_CAPF 6016 // 5120 overflowed by 2-140 rows in ~12 buckets per 32 nonces (recall_base.json, round 5); 6016 keeps two final-round WGs per CU
-#endif
-using Cfg200_9 = EhCfg<200, 9, 9, 4416, 1024, 512, 1024, 256, 4864, 5120, 1, BCP_EH_GEN_NT, BCP_EH_GEN_HPT, BCP_EH_CAPF, 0, BCP_EH_GW>;
-// (96,5): one extra pair slot per lane. ~1024 rows per bucket over 512 keys make ~1024 pairs, and
-// a list of 1280 overflowed in some bucket of most nonces: 84 + 18 + 36 + ~80 pairs per 16 nonces
-// in rounds 1-4, which pairs depending on the atomics' order, so a solution was lost now and then
-// (tools/eh_crosscheck.py --n 96 --k 5, profiles/equihash_r6.md).
-using Cfg96_5 = EhCfg<96, 5, 7, 1280, 256, 256, 256, 256, 1280, 1280, 1, 512, 2, 0, 1, 1>;
-using Cfg48_5 = EhCfg<48, 5, 3, 512, 64, 8, 64, 256>; // 512-slot areas: 8 pairs per lane (a 256-pair list overflowed on duplicate-heavy nonces)
-
-constexpr uint32_t NIL = 0xffffffffu;
 constexpr uint32_t OOB = 0x80000000u; // buffer offset past every descriptor's range: access dropped
 typedef uint32_t u2v __attribute__((ext_vector_type(2)));
 typedef uint32_t u3v __attribute__((ext_vector_type(3)));
@@ -481,12 +329,6 @@ __global__ __launch_bounds__(C::NTG) void eh_gen(const EhBaseState* __restrict__
 // tables, so several workgroups share a CU and one's hashing (VALU) overlaps another's
 // claim and scatter (memory) — the LDS-sorted eh_gen above holds a whole CU with its 118 KB
 // row buffer and runs those phases back to back.
-template <class C, int NTG, int HPT> struct GenReg {
-    static constexpr int RPT = HPT * C::IPH;            // rows per thread
-    static constexpr int RPW = NTG > 0 ? NTG * RPT : 1; // rows per workgroup
-    static constexpr bool OK = NTG > 0 && C::INIT % RPW == 0;
-    static constexpr int GWG = OK ? C::INIT / RPW : 1;  // workgroups per nonce
-};
 template <class C, bool HDR, int NTG, int HPT>
 __global__ __launch_bounds__(NTG) __attribute__((amdgpu_waves_per_eu(1))) void eh_gen_reg(const EhBaseState* __restrict__ states, uint32_t* __restrict__ R,
                                                   uint32_t* __restrict__ LEAF, uint32_t* __restrict__ CTR0, int items) {
@@ -581,20 +423,6 @@ __global__ __launch_bounds__(NTG) __attribute__((amdgpu_waves_per_eu(1))) void e
 }
 
 // ------------------------------------------------------------------ stages 1..K
-// Parent triple of a stage-s row (s >= 1): (producing bucket << 32) | (j << 16) | i; its parents
-// are the stage-(s-1) slots bucket*AREA + i and bucket*AREA + j.
-__device__ __forceinline__ uint64_t pack_tri(uint32_t d, uint32_t i, uint32_t j) {
-    return ((uint64_t)d << 32) | (j << 16) | i;
-}
-// Compact parent word (EhCfg::cp): i | j << 16, the spare high bits of each half holding d's bits
-// 0..DH-1 and DH..DX-1; d's bits DX.. ride in the low bits of the row's last word.
-template <class C> __host__ __device__ __forceinline__ uint32_t cpack(uint32_t d, uint32_t i, uint32_t j) {
-    return i | (j << 16) | ((d & C::DHM) << C::IB) | (((d >> C::DH) & C::DHM) << (16 + C::IB));
-}
-template <class C> __host__ __device__ __forceinline__ uint32_t cunpack_d(uint32_t pw, uint32_t lastword) {
-    return ((pw >> C::IB) & C::DHM) | (((pw >> (16 + C::IB)) & C::DHM) << C::DH) | ((lastword & C::RMASK) << C::DX);
-}
-
 // Diagnostic builds (STAMP) record s_memtime at each phase boundary (thread 0, after the
 // barrier) into `stamps` — never used by the production instantiation.
 #define EH_STAMP(k)                                                                                  \
@@ -604,62 +432,6 @@ template <class C> __host__ __device__ __forceinline__ uint32_t cunpack_d(uint32
         }                                                                                            \
     } while (0)
 
-// LDS bytes of a round. Phase-D union `un` (bytes): {sidx[CAP] u16, bend[NRESTS] u32, then the
-// pair list plist[MP*NT] u32} during the collision search; the slot -> pair table spair[MP*NT]
-// u32 (aliasing plist) after it.
-template <class C> constexpr int un_walk_bend(int cap) { return (cap * 2 + 3) / 4 * 4; }
-template <class C> constexpr int un_walk_list(int cap) { return un_walk_bend<C>(cap) + C::NRESTS * 4; }
-// Pairs per lane: one lane per LDS row slot, plus the configuration's MPX, plus BCP_EH_MP_LATE
-// extra from round BCP_EH_MP_LATE_FROM on ((200,9) only): without depth-1 pruning the late rounds'
-// pair lists grow past the row count (duplicate subtrees) and overflowed in round 8.
-// Round threads of a round workgroup: all NT, or NT - 64*GW in a round that carries generation
-// (the final round never carries: two of its workgroups share a CU and the generation tables
-// would not fit).
-template <class C> constexpr int round_nt(int stage, bool carry) { return carry && stage < C::K ? C::RNT : C::NT; }
-template <class C> constexpr int round_mp(int stage, bool carry) {
-    const int nt = round_nt<C>(stage, carry);
-    return stage == C::K ? 1
-                         : (C::AREA_NF + nt - 1) / nt + C::MPX +
-                               (C::K == 9 && stage >= BCP_EH_MP_LATE_FROM ? BCP_EH_MP_LATE : 0);
-}
-template <class C> constexpr int round_un(int stage, bool carry = false) {
-    const int cap = C::cap(stage);
-    if (stage == C::K) return un_walk_list<C>(cap); // final round: sidx and bend only
-    const int pairs = round_mp<C>(stage, carry) * round_nt<C>(stage, carry) * 4; // spair: every pair a lane may hold
-    const int walk = un_walk_list<C>(cap) + pairs; // + the pair list
-    return walk > pairs ? walk : pairs;
-}
-// (a carrying round adds the generation waves' two NB-entry tables and the round-0 prefix)
-template <class C> constexpr int round_lds(int stage, bool prune, bool carry = false) {
-    const int WR = C::words(stage - 1);
-    const int WI = WR; // LDS words per row
-    const int cap = C::cap(stage);
-    const int pruneb = prune ? cap * 4 + (C::cp(stage - 1) ? 0 : (cap * 2 + 3) / 4 * 4) : 0;
-    const int hists = stage == C::K ? 12 : 2 * C::HW * 4 + (C::NB * (C::H16 ? 2 : 4) + 3) / 4 * 4;
-    const int gen = carry ? 2 * C::NB * 4 + 16 * 8 : 0;
-    return (cap * WI + 3) / 4 * 16 + pruneb + 4 + round_un<C>(stage, carry) + hists +
-           (round_nt<C>(stage, carry) / 64 + 1) * 4 + gen;
-}
-// Depth-1 duplicate pruning wherever its parent words fit next to the full rows.
-template <class C> constexpr bool round_prunes(int stage, bool carry) {
-    // (the pruning start was measured on (200,9); the small configurations keep pruning from round 2)
-    constexpr int from = C::K == 9 ? BCP_EH_PRUNE_FROM : 2;
-    return (stage >= from || stage == C::K) && stage >= 2 && round_lds<C>(stage, true, carry) <= C::LDS_BUDGET;
-}
-
-// Generation carried by the collision rounds of the previous nonce group. The (K-1)*NB bucket
-// iterations that rounds 1..K-1 spend on a nonce hash that nonce's partner in the next group:
-// bucket d of round S generates chunk (S-1)*NB + d, CH consecutive hashes, HB per generation thread.
-template <class C> struct GenCarry {
-    static constexpr int GT = C::GW > 0 ? 64 * C::GW : 64;       // generation threads
-    static constexpr int NHASH = (C::INIT + C::IPH - 1) / C::IPH; // hashes per nonce
-    static constexpr int ITERS = (C::K - 1) * C::NB;
-    static constexpr int HB = ((NHASH + ITERS - 1) / ITERS + GT - 1) / GT;
-    static constexpr int CH = HB * GT;
-    static constexpr int RPT = HB * C::IPH;                       // rows per thread per chunk
-    static constexpr int BPT = (C::NB + GT - 1) / GT;             // run claims per thread
-    static_assert((long long)CH * ITERS >= NHASH, "the carrying rounds cover every hash");
-};
 // What a carrying round needs of the next group (all pointers already at that group's first nonce).
 struct EhCarry {
     const EhBaseState* states;
@@ -1462,37 +1234,27 @@ EhBaseState MakeEhBaseState(const CBlake2b& st_in) {
     return bs;
 }
 
+// Everything that depends on the configuration is a `template <class C>` member that reads the
+// layout from C:: (equihash_layout.h); the public methods forward to them through dispatch_cfg.
 struct EquihashGpuSolver::Impl {
     unsigned n, k;
     int batch, device;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_gen = nullptr, ev_rounds = nullptr; // this solver's last generation / rounds done (pipelining)
-    const Impl* after = nullptr;                        // Launch(states, prev): the batch to pipeline behind
     DevBuf<bcpk::EhBaseState> d_states;
     DevBuf<uint32_t> d_ctr, d_leaf, d_ncand, d_idx, d_valid, d_pdrop, d_nout, d_out;
     DevBuf<uint64_t> d_cand;
     DevBuf<uint32_t> d_rst[16]; // merged layout: stage-s slot arrays (s = 0..K-1)
     DevBuf<uint32_t> d_ptab[16], d_btab[16]; // stages with table parents: pair tables [nonce][d][ptab], run bases [nonce][d][b]
-    std::vector<bool> table;                 // per stage: table parents
-    std::vector<size_t> ptab_words;          // per stage: pair-table words per producing bucket
-    std::vector<uint32_t> tp_mask;           // per stage: padding bits eh_expand reads the producing bucket through
     HostBuf<bcpk::EhBaseState> h_states;
     HostBuf<uint32_t> h_ncand, h_idx, h_ctr0, h_ctr_all, h_pdrop, h_nout, h_out;
     size_t outq = 0; // compact-list entries copied back with every batch (more: a second copy)
-    size_t rows = 0, L = 0, maxcand = 0, nb = 0, kstages = 0;
-    std::vector<size_t> caps; // caps[s]: LDS capacity of the round that reads stage-s rows
-    std::vector<size_t> slot_words, row_words; // per stage
-    uint32_t cp_ib = 0, cp_dh = 0, cp_dhm = 0, cp_dx = 0, cp_rmask = 0, cp_imask = 0; // compact parent layout
-    std::vector<bool> compact;                  // per stage: compact parent word
     int inflight = 0;
     // LaunchPow / CollectPow (kernels/equihash_pow.h); the buffers are allocated by the first LaunchPow
     DevBuf<uint32_t> d_in140, d_powctr, d_win; // inputs of the batch's nonces; winners + repeats counters; winner list
     HostBuf<uint32_t> h_powctr, h_win;
-    size_t winw = 0;                        // words per winner entry
-    const bcpk::EhPowParams* pow = nullptr; // the job, while LaunchPow enqueues
-    bool pow_inflight = false;              // the launch in flight is a LaunchPow
-    bool pow_collect = false;               // Collect() is running for CollectPow()
+    bool pow_inflight = false; // the launch in flight is a LaunchPow
     EhPowJob pow_job;
     int ncu = 1;
     int groups = 1; // nonce groups of a launch (see launch()); 1: the whole batch is generated up front
@@ -1502,29 +1264,6 @@ struct EquihashGpuSolver::Impl {
     size_t bytes = 0;
 
     template <class C> void alloc() {
-        rows = C::ROWS;
-        L = C::L;
-        maxcand = C::MAXCAND;
-        nb = C::NB;
-        caps.clear();
-        for (int r = 1; r <= C::K; ++r) caps.push_back(C::cap(r));
-        slot_words.clear();
-        compact.clear();
-        row_words.clear();
-        for (int st = 0; st < C::K; ++st) {
-            slot_words.push_back(C::sw(st));
-            compact.push_back(C::cp(st));
-            row_words.push_back(C::words(st));
-        }
-        table.clear();
-        ptab_words.clear();
-        tp_mask.clear();
-        for (int st = 0; st < C::K; ++st) {
-            table.push_back(C::tp(st));
-            ptab_words.push_back(C::tp(st) ? C::ptab(st) : 0);
-            tp_mask.push_back(C::tp(st) ? C::tpmask(st) : 0u);
-        }
-        kstages = C::K;
         d_states.alloc(batch);
         h_states.alloc(batch);
         static_assert(C::K <= 16, "stage arrays");
@@ -1536,7 +1275,6 @@ struct EquihashGpuSolver::Impl {
             }
         d_ctr.alloc((size_t)C::K * batch * C::NB);
         d_leaf.alloc((size_t)batch * C::ROWS);
-        cp_ib = C::IB, cp_dh = C::DH, cp_dhm = C::DHM, cp_dx = C::DX, cp_rmask = C::RMASK, cp_imask = C::IMASK;
         d_ncand.alloc(batch);
         d_pdrop.alloc((size_t)batch * (2 * C::K + 2)); // per nonce, [1..K]: pair-list drops per round, [K+1..2K]: row drops per stage
         h_pdrop.alloc((size_t)batch * (2 * C::K + 2));
@@ -1567,62 +1305,76 @@ struct EquihashGpuSolver::Impl {
         }
         return std::min(nbk, ncu * per_cu);
     }
-    // Round S over the group of `gn` nonces that starts at nonce `noff`. With next > 0 (and S < K)
-    // the round carries the generation of the next group's first `next` nonces.
-    template <class C, int S> void launch_round(int noff, int gn, int next) {
-        const size_t o = (size_t)noff;
+    // Kernel eh_round<C, S, STAMP, CARRY> over the group of `gn` nonces that starts at nonce `noff`.
+    // CARRY: the round carries the generation of the next group's first `next` nonces.
+    template <class C, int S, bool STAMP, bool CARRY> void launch_round_as(int noff, int gn, int next) {
+        constexpr bool OUT = S < C::K;        // the final round writes candidates, no stage
+        constexpr int SO = S < C::K ? S : 0;  // the output stage
+        constexpr bool TP = OUT && C::tp(SO); // the output stage's parent tables
         constexpr size_t PDW = 2 * C::K + 2;
+        const size_t o = (size_t)noff;
         const uint32_t* rin = d_rst[S - 1].p + o * C::ROWS * C::sw(S - 1);
-        uint32_t* rout = S < C::K ? d_rst[S].p + o * C::ROWS * C::sw(S < C::K ? S : 0) : nullptr;
+        uint32_t* rout = OUT ? d_rst[SO].p + o * C::ROWS * C::sw(SO) : nullptr;
         const uint32_t* cin = d_ctr.p + ((size_t)(S - 1) * batch + o) * C::NB;
-        uint32_t* cout = S < C::K ? d_ctr.p + ((size_t)S * batch + o) * C::NB : nullptr;
-        constexpr bool TP = S < C::K && C::tp(S < C::K ? S : 0); // the output stage's parent tables
-        uint32_t* pout = TP ? d_ptab[S < C::K ? S : 0].p + o * C::NB * C::ptab(S < C::K ? S : 0) : nullptr;
-        uint32_t* bout = TP ? d_btab[S < C::K ? S : 0].p + o * C::NB * C::NB : nullptr;
-        uint32_t* nc = d_ncand.p + o;
-        uint64_t* cd = d_cand.p + o * C::MAXCAND;
+        uint32_t* cout = OUT ? d_ctr.p + ((size_t)S * batch + o) * C::NB : nullptr;
+        uint32_t* pout = TP ? d_ptab[SO].p + o * C::NB * C::ptab(SO) : nullptr;
+        uint32_t* bout = TP ? d_btab[SO].p + o * C::NB * C::NB : nullptr;
+        uint64_t* st = STAMP ? d_stamps.p + ((size_t)(S - 1) * batch + o) * C::NB * 16 : nullptr;
         const int nbk = C::NB * gn;
         bcpk::EhCarry cy{};
+        if constexpr (CARRY) {
+            const size_t p = o + (size_t)gn; // the next group's first nonce
+            cy.states = d_states.p + p;
+            cy.R0 = d_rst[0].p + p * C::ROWS * C::sw(0);
+            cy.LEAF = d_leaf.p + p * C::ROWS;
+            cy.CTR0 = d_ctr.p + p * C::NB;
+            cy.nonces = next;
+        }
+        hipLaunchKernelGGL((bcpk::eh_round<C, S, STAMP, CARRY>), dim3(round_grid<C, S, STAMP, CARRY>(nbk)), dim3(C::NT), 0,
+                           stream, rin, cin, rout, cout, pout, bout, d_ncand.p + o, d_cand.p + o * C::MAXCAND, st,
+                           d_pdrop.p + o * PDW, nbk, cy);
+    }
+    // Round S of a group. With next > 0 (and S < K) it carries the next group's generation; the
+    // stamped diagnostic rounds never carry.
+    template <class C, int S> void launch_round(int noff, int gn, int next) {
         if constexpr (C::GW > 0 && S < C::K) {
             if (next > 0 && !stamp_mode) {
-                const size_t p = o + (size_t)gn; // the next group's first nonce
-                cy.states = d_states.p + p;
-                cy.R0 = d_rst[0].p + p * C::ROWS * C::sw(0);
-                cy.LEAF = d_leaf.p + p * C::ROWS;
-                cy.CTR0 = d_ctr.p + p * C::NB;
-                cy.nonces = next;
-                hipLaunchKernelGGL((bcpk::eh_round<C, S, false, true>), dim3(round_grid<C, S, false, true>(nbk)),
-                                   dim3(C::NT), 0, stream, rin, cin, rout, cout, pout, bout, nc, cd, nullptr,
-                                   d_pdrop.p + o * PDW, nbk, cy);
+                launch_round_as<C, S, false, true>(noff, gn, next);
                 ++stats.carry_launches;
                 return;
             }
         }
-        if (stamp_mode) {
-            uint64_t* st = d_stamps.p + ((size_t)(S - 1) * batch + o) * C::NB * 16;
-            hipLaunchKernelGGL((bcpk::eh_round<C, S, true>), dim3(round_grid<C, S, true, false>(nbk)), dim3(C::NT), 0,
-                               stream, rin, cin, rout, cout, pout, bout, nc, cd, st, d_pdrop.p + o * PDW, nbk, cy);
-        } else {
-            hipLaunchKernelGGL((bcpk::eh_round<C, S, false>), dim3(round_grid<C, S, false, false>(nbk)), dim3(C::NT), 0,
-                               stream, rin, cin, rout, cout, pout, bout, nc, cd, nullptr, d_pdrop.p + o * PDW, nbk,
-                               cy);
-        }
+        if (stamp_mode) launch_round_as<C, S, true, false>(noff, gn, 0);
+        else launch_round_as<C, S, false, false>(noff, gn, 0);
     }
     template <class C, int... S> void launch_rounds(int noff, int gn, int next, std::integer_sequence<int, S...>) {
         (launch_round<C, S + 1>(noff, gn, next), ...);
     }
-
-    // what eh_expand walks: the slot arrays and, for the stages with table parents, their tables
-    template <class C> bcpk::EhStages stage_ptrs() const {
-        bcpk::EhStages st{};
-        for (int s = 0; s < C::K; ++s) st.r[s] = d_rst[s].p, st.p[s] = d_ptab[s].p, st.b[s] = d_btab[s].p;
-        return st;
+    // The stand-alone generation of the first gen_n nonces: the register kernel where the
+    // configuration's rows split evenly over its threads, else the LDS-sorted one.
+    template <class C, bool HDR> void launch_gen(int gen_n) {
+        using GR = bcpk::GenReg<C, C::GNT, C::GHPT>;
+        if constexpr (GR::OK) {
+            const int items = GR::GWG * gen_n;
+            hipLaunchKernelGGL((bcpk::eh_gen_reg<C, HDR, C::GNT, C::GHPT>), dim3(items), dim3(C::GNT), 0, stream, d_states.p,
+                               d_rst[0].p, d_leaf.p, d_ctr.p, items);
+        } else
+            hipLaunchKernelGGL((bcpk::eh_gen<C, HDR>), dim3(C::GENWG * gen_n), dim3(C::NTG), 0, stream, d_states.p,
+                               d_rst[0].p, d_leaf.p, d_ctr.p);
+    }
+    // The tree expansion of `nonces` nonces. It walks the slot arrays and, for the stages with
+    // table parents, their tables.
+    template <class C> void launch_expand(size_t nonces) {
+        constexpr int EB = C::L < 64 ? 64 : C::L;
+        bcpk::EhStages stages{};
+        for (int s = 0; s < C::K; ++s) stages.r[s] = d_rst[s].p, stages.p[s] = d_ptab[s].p, stages.b[s] = d_btab[s].p;
+        hipLaunchKernelGGL((bcpk::eh_expand<C>), dim3(C::MAXCAND * nonces), dim3(EB), 0, stream, d_leaf.p, stages,
+                           d_ncand.p, d_cand.p, d_idx.p, d_valid.p, d_nout.p, d_out.p);
     }
 
     template <class C> void alloc_pow() {
         using P = bcpk::PowCfg<C::N, C::K>;
         if (d_win.n) return;
-        winw = P::WINW;
         d_in140.alloc((size_t)batch * 35);
         d_powctr.alloc(2);
         h_powctr.alloc(2);
@@ -1630,11 +1382,14 @@ struct EquihashGpuSolver::Impl {
         h_win.alloc((size_t)batch * C::MAXCAND * P::WINW);
     }
 
-    template <class C> void launch(size_t nstates) {
+    // Enqueue one batch. pow: the LaunchPow job (states built and winners filtered on the device) or
+    // null; after: the solver whose batch this one is pipelined behind, or null.
+    template <class C> void launch(size_t nstates, const bcpk::EhPowParams* pow, const Impl* after) {
+        using P = bcpk::PowCfg<C::N, C::K>;
         if (pow) { // the states are built on the device
             BCP_HIP_CHECK(hipMemsetAsync(d_powctr.p, 0, 2 * sizeof(uint32_t), stream));
-            hipLaunchKernelGGL((bcpk::eh_nonce_states<bcpk::PowCfg<C::N, C::K>>), dim3(((int)nstates + 63) / 64), dim3(64),
-                               0, stream, *pow, (int)nstates, d_in140.p, d_states.p);
+            hipLaunchKernelGGL((bcpk::eh_nonce_states<P>), dim3(((int)nstates + 63) / 64), dim3(64), 0, stream, *pow,
+                               (int)nstates, d_in140.p, d_states.p);
         } else
             BCP_HIP_CHECK(hipMemcpyAsync(d_states.p, h_states.p, nstates * sizeof(bcpk::EhBaseState),
                                          hipMemcpyHostToDevice, stream));
@@ -1642,14 +1397,13 @@ struct EquihashGpuSolver::Impl {
         BCP_HIP_CHECK(hipMemsetAsync(d_nout.p, 0, sizeof(uint32_t), stream));
         BCP_HIP_CHECK(hipMemsetAsync(d_pdrop.p, 0, d_pdrop.n * sizeof(uint32_t), stream));
         BCP_HIP_CHECK(hipMemsetAsync(d_ctr.p, 0, d_ctr.n * sizeof(uint32_t), stream));
-        if (debug) {
-            if (d_leaf.n) BCP_HIP_CHECK(hipMemsetAsync(d_leaf.p, 0xff, d_leaf.n * sizeof(uint32_t), stream));
-            for (int s = 0; s < C::K; ++s)
-                if (d_rst[s].n) BCP_HIP_CHECK(hipMemsetAsync(d_rst[s].p, 0xff, d_rst[s].n * sizeof(uint32_t), stream));
-            for (int s = 0; s < C::K; ++s) {
-                if (d_ptab[s].n) BCP_HIP_CHECK(hipMemsetAsync(d_ptab[s].p, 0xff, d_ptab[s].n * sizeof(uint32_t), stream));
-                if (d_btab[s].n) BCP_HIP_CHECK(hipMemsetAsync(d_btab[s].p, 0xff, d_btab[s].n * sizeof(uint32_t), stream));
-            }
+        if (debug) { // never-written slots and table entries read all-ones
+            auto ones = [&](DevBuf<uint32_t>& b) {
+                if (b.n) BCP_HIP_CHECK(hipMemsetAsync(b.p, 0xff, b.n * sizeof(uint32_t), stream));
+            };
+            ones(d_leaf);
+            for (int s = 0; s < C::K; ++s) ones(d_rst[s]);
+            for (int s = 0; s < C::K; ++s) ones(d_ptab[s]), ones(d_btab[s]);
         }
         BCP_HIP_CHECK(hipEventRecord(ev0, stream));
         // header-shaped inputs (140 B: g lands at byte 12 of the final block) take the
@@ -1670,40 +1424,19 @@ struct EquihashGpuSolver::Impl {
             if (gsz >= bcpk::NXCD) gsz = (gsz + bcpk::NXCD - 1) / bcpk::NXCD * bcpk::NXCD; // keeps the XCD mapping
         }
         const int gen_n = std::min(gsz, (int)nstates); // nonces of the stand-alone generation
-        uint32_t* r0 = d_rst[0].p;
-        hipStream_t gs = stream;
-        if (after) BCP_HIP_CHECK(hipStreamWaitEvent(gs, after->ev_gen, 0)); // one generation at a time
-        constexpr bool reg = bcpk::GenReg<C, C::GNT, C::GHPT>::OK;
-        if constexpr (reg) {
-            using GR = bcpk::GenReg<C, C::GNT, C::GHPT>;
-            const int items = GR::GWG * gen_n;
-            const int grid = items;
-            if (hdr)
-                hipLaunchKernelGGL((bcpk::eh_gen_reg<C, true, C::GNT, C::GHPT>), dim3(grid), dim3(C::GNT), 0, gs,
-                                   d_states.p, r0, d_leaf.p, d_ctr.p, items);
-            else
-                hipLaunchKernelGGL((bcpk::eh_gen_reg<C, false, C::GNT, C::GHPT>), dim3(grid), dim3(C::GNT), 0, gs,
-                                   d_states.p, r0, d_leaf.p, d_ctr.p, items);
-        } else if (hdr)
-            hipLaunchKernelGGL((bcpk::eh_gen<C, true>), dim3(C::GENWG * gen_n), dim3(C::NTG), 0, gs,
-                               d_states.p, r0, d_leaf.p, d_ctr.p);
-        else
-            hipLaunchKernelGGL((bcpk::eh_gen<C, false>), dim3(C::GENWG * gen_n), dim3(C::NTG), 0, gs,
-                               d_states.p, r0, d_leaf.p, d_ctr.p);
-        BCP_HIP_CHECK(hipEventRecord(ev_gen, gs));
+        if (after) BCP_HIP_CHECK(hipStreamWaitEvent(stream, after->ev_gen, 0)); // one generation at a time
+        if (hdr) launch_gen<C, true>(gen_n);
+        else launch_gen<C, false>(gen_n);
+        BCP_HIP_CHECK(hipEventRecord(ev_gen, stream));
         if (after) BCP_HIP_CHECK(hipStreamWaitEvent(stream, after->ev_rounds, 0)); // one round chain at a time
         for (int noff = 0; noff < (int)nstates; noff += gsz) {
             const int gn = std::min(gsz, (int)nstates - noff);
             const int next = std::max(0, std::min(gsz, (int)nstates - noff - gsz));
             launch_rounds<C>(noff, gn, next, std::make_integer_sequence<int, C::K>{});
         }
-        constexpr int EB = C::L < 64 ? 64 : C::L;
-        const bcpk::EhStages stages = stage_ptrs<C>();
-        hipLaunchKernelGGL((bcpk::eh_expand<C>), dim3(C::MAXCAND * nstates), dim3(EB), 0, stream, d_leaf.p, stages,
-                           d_ncand.p, d_cand.p, d_idx.p, d_valid.p, d_nout.p, d_out.p);
+        launch_expand<C>(nstates);
         BCP_HIP_CHECK(hipEventRecord(ev_rounds, stream));
         if (pow) {
-            using P = bcpk::PowCfg<C::N, C::K>;
             const int grid = (int)std::min<size_t>(C::MAXCAND * nstates, 2048); // grid-stride over the entries
             hipLaunchKernelGGL((bcpk::eh_pow_filter<P>), dim3(grid), dim3(64), 0, stream, *pow, (int)nstates, d_in140.p,
                                d_nout.p, d_out.p, (uint32_t)(C::MAXCAND * nstates), d_powctr.p, d_win.p, debug ? 1 : 0);
@@ -1723,7 +1456,7 @@ struct EquihashGpuSolver::Impl {
         BCP_HIP_CHECK(hipMemcpyAsync(h_nout.p, d_nout.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         if (pow) { // the winners instead of the index lists
             BCP_HIP_CHECK(hipMemcpyAsync(h_powctr.p, d_powctr.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            BCP_HIP_CHECK(hipMemcpyAsync(h_win.p, d_win.p, outq * winw * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            BCP_HIP_CHECK(hipMemcpyAsync(h_win.p, d_win.p, outq * P::WINW * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         } else
             BCP_HIP_CHECK(hipMemcpyAsync(h_out.p, d_out.p, outq * (C::L + 2) * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                          stream));
@@ -1731,14 +1464,336 @@ struct EquihashGpuSolver::Impl {
             BCP_HIP_CHECK(hipMemcpyAsync(h_idx.p, d_idx.p, C::MAXCAND * C::L * sizeof(uint32_t),
                                          hipMemcpyDeviceToHost, stream));
     }
-};
 
-template <class F> static void dispatch_cfg(unsigned n, unsigned k, F&& f) {
-    if (n == 200 && k == 9) f(bcpk::Cfg200_9{});
-    else if (n == 96 && k == 5) f(bcpk::Cfg96_5{});
-    else if (n == 48 && k == 5) f(bcpk::Cfg48_5{});
-    else throw std::invalid_argument("EquihashGpuSolver: unsupported (N,K); GPU supports (200,9),(96,5),(48,5)");
-}
+    // What a public method returns: f(C{}) of this solver's configuration C.
+    template <class R, class F> R with_cfg(F&& f) {
+        R out;
+        dispatch_cfg(n, k, [&](auto c) { out = f(c); });
+        return out;
+    }
+    // The solver a launch is pipelined behind, checked.
+    const Impl* behind(const EquihashGpuSolver& prev) const {
+        if (prev.impl.get() == this) throw std::invalid_argument("EquihashGpuSolver: cannot pipeline behind itself");
+        if (prev.impl->device != device) throw std::invalid_argument("EquihashGpuSolver: pipelined solvers on different devices");
+        return prev.impl.get();
+    }
+    void launch_states(const std::vector<EhBaseState>& states, const Impl* after) {
+        if (states.empty() || (int)states.size() > batch) throw std::invalid_argument("bad number of states");
+        if (inflight) throw std::runtime_error("EquihashGpuSolver: Collect() the previous launch first");
+        BCP_HIP_CHECK(hipSetDevice(device));
+        memcpy(h_states.p, states.data(), states.size() * sizeof(EhBaseState));
+        dispatch_cfg(n, k, [&](auto c) { launch<decltype(c)>(states.size(), nullptr, after); });
+        inflight = (int)states.size();
+    }
+    void launch_pow(const EhPowJob& job, const Impl* after) {
+        if (job.count < 1 || job.count > batch) throw std::invalid_argument("LaunchPow: count must be 1..Batch()");
+        if (inflight) throw std::runtime_error("EquihashGpuSolver: Collect() the previous launch first");
+        BCP_HIP_CHECK(hipSetDevice(device));
+        bcpk::EhPowParams p;
+        static_assert(sizeof(p.prefix) == sizeof(job.prefix) && sizeof(p.nonce) == 32 && sizeof(p.target) == 32, "job words");
+        memcpy(p.prefix, job.prefix, sizeof(p.prefix));
+        memcpy(p.nonce, job.nonce_first, 32);
+        memcpy(p.target, job.target_le, 32);
+        dispatch_cfg(n, k, [&](auto c) {
+            alloc_pow<decltype(c)>();
+            launch<decltype(c)>((size_t)job.count, &p, after);
+        });
+        pow_job = job;
+        pow_inflight = true;
+        inflight = job.count;
+    }
+
+    // The end of a launch, for Collect and CollectPow: the wait, the event time, the drop and fill
+    // statistics and the candidate counts. Returns the number of nonces that were in flight.
+    template <class C> int finish() {
+        pow_inflight = false;
+        BCP_HIP_CHECK(hipSetDevice(device));
+        BCP_HIP_CHECK(hipStreamSynchronize(stream));
+        const int ns = inflight;
+        inflight = 0;
+        float ms = 0;
+        BCP_HIP_CHECK(hipEventElapsedTime(&ms, ev0, ev1));
+        stats.gpu_ms += ms;
+        stats.nonces += ns;
+        constexpr size_t K = C::K, NB = C::NB;
+        // every nonce: pair-list drops per round and rows past a round's capacity per stage (accumulated)
+        stats.pair_dropped_all.resize(K + 1, 0);
+        stats.stage_dropped_all.resize(K, 0);
+        stats.pair_dropped_nonce.assign(ns, 0);
+        stats.stage_dropped_nonce.assign(ns, 0);
+        std::vector<uint64_t> pd(K + 1, 0);
+        for (int nn = 0; nn < ns; ++nn) {
+            const uint32_t* q = h_pdrop.p + (size_t)nn * (2 * K + 2);
+            for (size_t r = 0; r <= K; ++r) {
+                pd[r] += q[r];
+                stats.pair_dropped_all[r] += q[r];
+                stats.pair_dropped_nonce[nn] += q[r];
+            }
+            for (size_t s = 0; s < K; ++s) {
+                stats.stage_dropped_all[s] += q[K + 1 + s];
+                stats.stage_dropped_nonce[nn] += q[K + 1 + s];
+            }
+        }
+        if (debug) stats.pair_dropped = pd;
+        if (debug) {
+            // nonce 0: per stage, rows offered to each bucket (its fill counter) vs the LDS capacity
+            // of the round that reads it
+            stats.stage_rows.assign(K, 0);
+            stats.stage_dropped.assign(K, 0);
+            stats.stage_maxfill.assign(K, 0);
+            stats.stage_top.assign(K, {});
+            // every nonce of the batch: the fullest bucket per stage and the buckets past capacity
+            stats.stage_maxfill_all.assign(K, 0);
+            for (size_t s = 0; s < K; ++s)
+                for (size_t x = 0; x < (size_t)ns * NB; ++x) {
+                    const uint64_t fill = h_ctr_all.p[(s * batch) * NB + x];
+                    stats.stage_maxfill_all[s] = std::max<uint64_t>(stats.stage_maxfill_all[s], fill);
+                    if (fill > (uint64_t)C::cap(s + 1)) stats.overflow_fills.push_back((uint64_t)s << 32 | fill);
+                }
+            for (size_t s = 0; s < K; ++s) {
+                const uint64_t cap = C::cap(s + 1);
+                std::vector<uint64_t> fills;
+                for (size_t dd = 0; dd < NB; ++dd) {
+                    const uint64_t fill = h_ctr0.p[s * NB + dd];
+                    fills.push_back(fill);
+                    stats.stage_rows[s] += fill;
+                    stats.stage_maxfill[s] = std::max<uint64_t>(stats.stage_maxfill[s], fill);
+                    if (fill > cap) {
+                        stats.stage_dropped[s] += fill - cap;
+                        stats.dropped_rows += fill - cap;
+                    }
+                }
+                std::sort(fills.rbegin(), fills.rend());
+                fills.resize(std::min<size_t>(fills.size(), 8));
+                stats.stage_top[s] = fills;
+            }
+            stats.debug_cands.clear();
+            const uint32_t nc = std::min<uint32_t>(h_ncand.p[0], (uint32_t)C::MAXCAND);
+            for (uint32_t c = 0; c < nc; ++c) {
+                const uint32_t* p = h_idx.p + (size_t)c * C::L;
+                stats.debug_cands.emplace_back(p, p + C::L);
+            }
+        }
+        uint64_t cands = 0;
+        for (int nn = 0; nn < ns; ++nn) {
+            const uint32_t c = h_ncand.p[nn];
+            cands += std::min<uint32_t>(c, (uint32_t)C::MAXCAND);
+            stats.cand_max = std::max<uint64_t>(stats.cand_max, c);
+            if (c > (uint32_t)C::MAXCAND) stats.cand_dropped += c - C::MAXCAND; // lost candidates, maybe solutions
+        }
+        stats.candidates += cands;
+        stats.duplicates += cands - h_nout.p[0];
+        return ns;
+    }
+
+    template <class C> std::vector<std::vector<std::vector<uint32_t>>> collect() {
+        const int ns = finish<C>();
+        std::vector<std::vector<std::vector<uint32_t>>> out(ns);
+        constexpr size_t ew = C::L + 2; // compact-list entry: nonce, candidate, L indices
+        const size_t nout = h_nout.p[0];
+        if (nout > outq) // more valid solutions than the per-batch copy holds: fetch the rest
+            BCP_HIP_CHECK(hipMemcpy(h_out.p + outq * ew, d_out.p + outq * ew, (nout - outq) * ew * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost));
+        // the list is in completion order: put every nonce's solutions in candidate order
+        std::vector<std::pair<uint64_t, const uint32_t*>> ents;
+        ents.reserve(nout);
+        for (size_t e = 0; e < nout; ++e) {
+            const uint32_t* p = h_out.p + e * ew;
+            if (p[0] < (uint32_t)ns) ents.emplace_back(((uint64_t)p[0] << 32) | p[1], p + 2);
+        }
+        std::sort(ents.begin(), ents.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (const auto& en : ents) {
+            const int nn = (int)(en.first >> 32);
+            std::vector<uint32_t> v(en.second, en.second + C::L);
+            bool seen = false;
+            for (auto& prev : out[nn]) seen |= (prev == v);
+            if (seen) continue;
+            out[nn].push_back(std::move(v));
+            stats.solutions++;
+        }
+        return out;
+    }
+
+    // The winners of a LaunchPow (the index lists stayed on the device).
+    template <class C> EhPowResult collect_pow() {
+        constexpr size_t winw = bcpk::PowCfg<C::N, C::K>::WINW; // words per winner entry
+        const int ns = finish<C>();
+        const size_t nout = h_nout.p[0], nwin = h_powctr.p[0], ndup = h_powctr.p[1];
+        if (nwin > outq) // more winners than the per-batch copy holds: fetch the rest
+            BCP_HIP_CHECK(hipMemcpy(h_win.p + outq * winw, d_win.p + outq * winw, (nwin - outq) * winw * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost));
+        EhPowResult res;
+        res.solutions = nout - ndup;
+        stats.solutions += res.solutions;
+        const size_t solw = (winw - 11) * 4;
+        // the list is in completion order: by position in the nonce range, then by hash as an integer
+        std::vector<const uint32_t*> ents;
+        for (size_t e = 0; e < nwin; ++e) {
+            const uint32_t* p = h_win.p + e * winw;
+            if (p[0] < (uint32_t)ns) ents.push_back(p);
+        }
+        std::sort(ents.begin(), ents.end(), [](const uint32_t* a, const uint32_t* b) {
+            if (a[0] != b[0]) return a[0] < b[0];
+            for (int i = 7; i >= 0; --i)
+                if (a[3 + i] != b[3 + i]) return a[3 + i] < b[3 + i];
+            return a[1] < b[1];
+        });
+        for (const uint32_t* p : ents) {
+            EhPowHit h;
+            uint64_t carry = p[0];
+            for (int q = 0; q < 4; ++q) { // nonce_first + position, 256-bit little-endian
+                uint64_t a;
+                memcpy(&a, pow_job.nonce_first + 8 * q, 8);
+                const uint64_t s = a + carry;
+                carry = s < a ? 1 : 0;
+                memcpy(h.nonce + 8 * q, &s, 8);
+            }
+            memcpy(h.hash, p + 3, 32);
+            h.solution.assign(reinterpret_cast<const unsigned char*>(p + 11), reinterpret_cast<const unsigned char*>(p + 11) + solw);
+            if (debug) {
+                res.all.push_back(h);
+                res.all_pass.push_back(p[2] ? 1 : 0);
+            }
+            if (p[2]) res.hits.push_back(std::move(h));
+        }
+        return res;
+    }
+
+    // Mean cycles per phase per round (diagnostic stamp builds): [stage][phase delta], deltas
+    // 1..6 = commit, next-bucket issue + barrier, key sort, pair enumeration, claim + pair sort, emit;
+    // [0] = whole bucket.
+    template <class C> std::vector<std::vector<double>> phase_cycles(int nonces) {
+        BCP_HIP_CHECK(hipSetDevice(device));
+        BCP_HIP_CHECK(hipStreamSynchronize(stream));
+        const size_t per = (size_t)batch * C::NB * 16;
+        std::vector<uint64_t> h(C::K * per);
+        BCP_HIP_CHECK(hipMemcpy(h.data(), d_stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<std::vector<double>> out;
+        for (size_t s = 0; s < (size_t)C::K; ++s) {
+            // phases 1..6, then D2 split at stamp 7: listing (3 -> 7) and filtering (7 -> 4)
+            std::vector<double> acc(9, 0.0);
+            size_t cnt = 0;
+            for (size_t wg = 0; wg < (size_t)nonces * C::NB; ++wg) {
+                const uint64_t* t = &h[s * per + wg * 16];
+                if (t[0] == 0) continue;
+                for (int k = 1; k < 7; ++k) // (a phase counts when both of its stamps were taken)
+                    if (t[k] >= t[k - 1] && t[k - 1] != 0) acc[k] += (double)(t[k] - t[k - 1]);
+                acc[0] += (double)(t[6] - t[0]);
+                if (t[7] >= t[3] && t[4] >= t[7] && t[7] != 0) {
+                    acc[7] += (double)(t[7] - t[3]);
+                    acc[8] += (double)(t[4] - t[7]);
+                }
+                ++cnt;
+            }
+            for (auto& a : acc) a = cnt ? a / cnt : 0;
+            out.push_back(acc);
+        }
+        return out;
+    }
+
+    // Debug mode: one nonce of the last batch, its bucket fill counters (rows offered to each bucket),
+    // K stages of NB.
+    template <class C> std::vector<uint32_t> debug_fills(int nonce) {
+        if (!debug || nonce < 0 || nonce >= batch) throw std::invalid_argument("DebugFills: debug mode and a nonce of the batch");
+        BCP_HIP_CHECK(hipSetDevice(device));
+        BCP_HIP_CHECK(hipStreamSynchronize(stream));
+        std::vector<uint32_t> out;
+        for (size_t s = 0; s < (size_t)C::K; ++s) {
+            const uint32_t* p = h_ctr_all.p + (s * batch + nonce) * C::NB;
+            out.insert(out.end(), p, p + C::NB);
+        }
+        return out;
+    }
+
+    // Debug: one nonce of the last batch, K arrays of ROWS slots: stage-0 leaf indices (zero-extended),
+    // then the parent triples of stages 1..K-1; with SetDebug(true) never-written slots read all-ones.
+    template <class C> std::vector<uint64_t> debug_dump(int nonce) {
+        if (nonce < 0 || nonce >= batch) throw std::invalid_argument("DebugDump: nonce outside the batch");
+        BCP_HIP_CHECK(hipSetDevice(device));
+        BCP_HIP_CHECK(hipStreamSynchronize(stream));
+        constexpr size_t R = C::ROWS, NB = C::NB;
+        std::vector<uint64_t> out(C::K * R);
+        std::vector<uint32_t> leaf(R);
+        BCP_HIP_CHECK(hipMemcpy(leaf.data(), d_leaf.p + (size_t)nonce * R, R * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < R; ++i) out[i] = leaf[i];
+        for (int s = 1; s < C::K; ++s) {
+            const size_t sw = C::sw(s), w = C::words(s), pw = C::ptab(s);
+            std::vector<uint32_t> buf(R * sw), bt, pt;
+            BCP_HIP_CHECK(hipMemcpy(buf.data(), d_rst[s].p + (size_t)nonce * R * sw, R * sw * 4, hipMemcpyDeviceToHost));
+            if (C::tp(s)) { // the triple through the run-base and pair tables, as eh_expand walks it
+                bt.resize(NB * NB), pt.resize(NB * pw);
+                BCP_HIP_CHECK(hipMemcpy(bt.data(), d_btab[s].p + (size_t)nonce * NB * NB, bt.size() * 4, hipMemcpyDeviceToHost));
+                BCP_HIP_CHECK(hipMemcpy(pt.data(), d_ptab[s].p + (size_t)nonce * NB * pw, pt.size() * 4, hipMemcpyDeviceToHost));
+            }
+            for (size_t i = 0; i < R; ++i) {
+                const uint32_t* slot = &buf[i * sw];
+                // A slot never written keeps the SetDebug fill. Table parents: in every row word (a
+                // row ends in zero padding above its producing bucket, or is not all-ones with
+                // overwhelming odds); else in its parent word (no LDS row index is all-ones).
+                bool unwritten = C::tp(s) || (C::cp(s) && slot[w] == bcpk::NIL), in_range;
+                for (size_t x = 0; x < w && C::tp(s); ++x) unwritten &= slot[x] == bcpk::NIL;
+                out[s * R + i] = unwritten   ? ~0ull
+                                 : C::tp(s) ? bcpk::table_parent<C>(s, slot, i / C::AREA, i % C::AREA, bt.data(), pt.data(), &in_range)
+                                            : bcpk::slot_parent<C>(s, slot);
+            }
+        }
+        return out;
+    }
+
+    // DebugExpandCorrupt (gpu_api.h): corrupt one parent of nonce 0's first candidate, expand again.
+    template <class C> std::vector<uint32_t> debug_expand_corrupt(int mode) {
+        BCP_HIP_CHECK(hipSetDevice(device));
+        BCP_HIP_CHECK(hipStreamSynchronize(stream));
+        uint32_t nc = 0;
+        BCP_HIP_CHECK(hipMemcpy(&nc, d_ncand.p, 4, hipMemcpyDeviceToHost));
+        nc = std::min<uint32_t>(nc, (uint32_t)C::MAXCAND);
+        if (nc == 0) return {};
+        uint64_t tri = 0;
+        BCP_HIP_CHECK(hipMemcpy(&tri, d_cand.p, 8, hipMemcpyDeviceToHost));
+        constexpr int ST = C::K - 1; // the stage the final round read: its slots carry their parent word(s)
+        static_assert(!C::tp(ST), "the last stage keeps its parents in the slots");
+        const uint32_t d = (uint32_t)(tri >> 32), i = (uint32_t)tri & 0xffff;
+        uint32_t* slot = d_rst[ST].p + ((size_t)d * C::AREA + i) * C::sw(ST);
+        uint32_t w[C::sw(ST)] = {};
+        if (mode != 0) BCP_HIP_CHECK(hipMemcpy(w, slot, sizeof(w), hipMemcpyDeviceToHost));
+        uint32_t* pw = w + C::words(ST); // the parent word(s)
+        if (mode == 3 || mode == 4) {
+            // The table walk of a stage-(K-2) parent of the first candidate: mode 3 sets a padding bit
+            // above the producing bucket in its row (a bucket >= NB), mode 4 rewrites the run base of
+            // its (bucket, area) so that the slot's ordinal is the first one past the pair table.
+            if (ST < 2 || !C::tp(ST - 1) || C::tpmask(ST - 1) < (uint32_t)C::NB)
+                throw std::invalid_argument("DebugExpandCorrupt: modes 3 and 4 need table parents with spare padding in stage K-2");
+            const uint64_t par = bcpk::slot_parent<C>(ST, w); // the slot's left parent: area d1, position i1
+            const uint32_t d1 = (uint32_t)(par >> 32), i1 = (uint32_t)par & 0xffff;
+            if (d1 >= (uint32_t)C::NB || i1 >= (uint32_t)C::AREA) throw std::runtime_error("DebugExpandCorrupt: the first candidate's parent is out of range");
+            uint32_t* lw = d_rst[ST - 1].p + ((size_t)d1 * C::AREA + i1) * C::sw(ST - 1) + C::words(ST - 1) - 1;
+            uint32_t x = 0;
+            BCP_HIP_CHECK(hipMemcpy(&x, lw, 4, hipMemcpyDeviceToHost));
+            if (mode == 3) {
+                x |= (uint32_t)C::NB;
+                BCP_HIP_CHECK(hipMemcpy(lw, &x, 4, hipMemcpyHostToDevice));
+            } else {
+                const uint32_t d2 = x & C::tpmask(ST - 1);
+                if (d2 >= (uint32_t)C::NB) throw std::runtime_error("DebugExpandCorrupt: the parent row's bucket is out of range");
+                const uint32_t rb = i1 - (uint32_t)C::ptab(ST - 1);
+                BCP_HIP_CHECK(hipMemcpy(d_btab[ST - 1].p + (size_t)d2 * C::NB + d1, &rb, 4, hipMemcpyHostToDevice));
+            }
+        } else if (mode != 0) {
+            if (C::cp(ST)) // compact word: i | j << 16 with the bucket's bits in the spare high bits of each half
+                pw[0] = mode == 1 ? (pw[0] | (C::DHM << C::IB) | (C::DHM << (16 + C::IB))) : (pw[0] | ((1u << C::IB) - 1));
+            else if (mode == 1) pw[1] = 0xffffu;          // producing bucket far past NB
+            else pw[0] = (pw[0] & 0xffff0000u) | 0xffffu; // LDS row far past the area
+            BCP_HIP_CHECK(hipMemcpy(slot + C::words(ST), pw, (C::sw(ST) - C::words(ST)) * 4, hipMemcpyHostToDevice));
+        }
+        BCP_HIP_CHECK(hipMemsetAsync(d_nout.p, 0, 4, stream));
+        launch_expand<C>(1);
+        BCP_HIP_CHECK(hipGetLastError());
+        BCP_HIP_CHECK(hipStreamSynchronize(stream));
+        std::vector<uint32_t> valid(nc);
+        BCP_HIP_CHECK(hipMemcpy(valid.data(), d_valid.p, nc * 4, hipMemcpyDeviceToHost));
+        return valid;
+    }
+};
 
 EquihashGpuSolver::EquihashGpuSolver(unsigned n, unsigned k, int batch, int device) : impl(new Impl) {
     if (batch < 1) throw std::invalid_argument("batch must be >= 1");
@@ -1776,399 +1831,48 @@ unsigned EquihashGpuSolver::K() const { return impl->k; }
 int EquihashGpuSolver::Batch() const { return impl->batch; }
 const EhGpuStats& EquihashGpuSolver::Stats() const { return impl->stats; }
 void EquihashGpuSolver::SetDebug(bool on) { impl->debug = on; }
-void EquihashGpuSolver::SetStampMode(bool on) { impl->stamp_mode = on; }
-
-// Mean cycles per phase per round (diagnostic stamp builds): [stage][phase delta], deltas
-// 1..6 = commit, next-bucket issue + barrier, key sort, pair enumeration, claim + pair sort, emit;
-// [0] = whole bucket.
-std::vector<std::vector<double>> EquihashGpuSolver::PhaseCycles(int nonces) {
-    BCP_HIP_CHECK(hipSetDevice(impl->device));
-    BCP_HIP_CHECK(hipStreamSynchronize(impl->stream));
-    const size_t per = (size_t)impl->batch * impl->nb * 16;
-    std::vector<uint64_t> h(impl->kstages * per);
-    BCP_HIP_CHECK(hipMemcpy(h.data(), impl->d_stamps.p, h.size() * 8, hipMemcpyDeviceToHost));
-    std::vector<std::vector<double>> out;
-    for (size_t s = 0; s < impl->kstages; ++s) {
-        // phases 1..6, then D2 split at stamp 7: listing (3 -> 7) and filtering (7 -> 4)
-        std::vector<double> acc(9, 0.0);
-        size_t cnt = 0;
-        for (size_t wg = 0; wg < (size_t)nonces * impl->nb; ++wg) {
-            const uint64_t* t = &h[s * per + wg * 16];
-            if (t[0] == 0) continue;
-            for (int k = 1; k < 7; ++k)
-                if (t[k] >= t[k - 1] && t[k] != 0) acc[k] += (double)(t[k] - t[k - 1]);
-            acc[0] += (double)(t[6] - t[0]);
-            if (t[7] >= t[3] && t[4] >= t[7] && t[7] != 0) {
-                acc[7] += (double)(t[7] - t[3]);
-                acc[8] += (double)(t[4] - t[7]);
-            }
-            ++cnt;
-        }
-        for (auto& a : acc) a = cnt ? a / cnt : 0;
-        out.push_back(acc);
+void EquihashGpuSolver::SetStampMode(bool on) {
+    impl->stamp_mode = on;
+    if (on) { // a stamp no kernel writes (the final round has no phases 4, 5 and 7) reads as zero: PhaseCycles skips it
+        BCP_HIP_CHECK(hipSetDevice(impl->device));
+        BCP_HIP_CHECK(hipMemsetAsync(impl->d_stamps.p, 0, impl->d_stamps.n * sizeof(uint64_t), impl->stream));
     }
-    return out;
 }
 void EquihashGpuSolver::ResetStats() { impl->stats = EhGpuStats(); }
-
-// Debug mode: one nonce of the last batch, its bucket fill counters (rows offered to each bucket),
-// K stages of NB.
-std::vector<uint32_t> EquihashGpuSolver::DebugFills(int nonce) {
-    const Impl& m = *impl;
-    if (!m.debug || nonce < 0 || nonce >= m.batch) throw std::invalid_argument("DebugFills: debug mode and a nonce of the batch");
-    BCP_HIP_CHECK(hipSetDevice(m.device));
-    BCP_HIP_CHECK(hipStreamSynchronize(m.stream));
-    std::vector<uint32_t> out;
-    for (size_t s = 0; s < m.kstages; ++s) {
-        const uint32_t* p = m.h_ctr_all.p + (s * m.batch + nonce) * m.nb;
-        out.insert(out.end(), p, p + m.nb);
-    }
-    return out;
-}
-
-// Debug: one nonce of the last batch, K arrays of ROWS slots: stage-0 leaf indices (zero-extended),
-// then the parent triples of stages 1..K-1; with SetDebug(true) never-written slots read all-ones.
-std::vector<uint64_t> EquihashGpuSolver::DebugDump(int nonce) {
-    if (nonce < 0 || nonce >= impl->batch) throw std::invalid_argument("DebugDump: nonce outside the batch");
-    BCP_HIP_CHECK(hipSetDevice(impl->device));
-    BCP_HIP_CHECK(hipStreamSynchronize(impl->stream));
-    const Impl& m = *impl;
-    const size_t R = m.rows, K = m.kstages;
-    std::vector<uint64_t> out(K * R);
-    std::vector<uint32_t> leaf(R);
-    BCP_HIP_CHECK(hipMemcpy(leaf.data(), m.d_leaf.p + (size_t)nonce * R, R * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < R; ++i) out[i] = leaf[i];
-    // the parent word(s) follow the row in every stage-s slot without table parents (bcpk::cpack layout)
-    auto cunpack_d = [&](uint32_t pw, uint32_t last) {
-        return ((pw >> m.cp_ib) & m.cp_dhm) | (((pw >> (16 + m.cp_ib)) & m.cp_dhm) << m.cp_dh) |
-               ((last & m.cp_rmask) << m.cp_dx);
-    };
-    for (size_t s = 1; s < K; ++s) {
-        const size_t sw = m.slot_words[s], w = m.row_words[s];
-        std::vector<uint32_t> buf(R * sw);
-        BCP_HIP_CHECK(hipMemcpy(buf.data(), m.d_rst[s].p + (size_t)nonce * R * sw, R * sw * 4, hipMemcpyDeviceToHost));
-        if (m.table[s]) {
-            // table parents: the triple through the run-base and pair tables, as eh_expand walks it;
-            // a slot never written keeps the SetDebug fill in every row word (a row ends in zero
-            // padding above its producing bucket, or is not all-ones with overwhelming odds)
-            const size_t NB = m.nb, area = R / NB, pw = m.ptab_words[s];
-            std::vector<uint32_t> bt(NB * NB), pt(NB * pw);
-            BCP_HIP_CHECK(hipMemcpy(bt.data(), m.d_btab[s].p + (size_t)nonce * NB * NB, bt.size() * 4, hipMemcpyDeviceToHost));
-            BCP_HIP_CHECK(hipMemcpy(pt.data(), m.d_ptab[s].p + (size_t)nonce * NB * pw, pt.size() * 4, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < R; ++i) {
-                const uint32_t* row = &buf[i * sw];
-                bool unwritten = true;
-                for (size_t x = 0; x < w; ++x) unwritten &= row[x] == 0xffffffffu;
-                const uint32_t d = row[w - 1] & m.tp_mask[s];
-                const uint32_t t = d < NB ? (uint32_t)(i % area) - bt[d * NB + i / area] : 0u;
-                if (unwritten)
-                    out[s * R + i] = ~0ull;
-                else // (a bucket or an ordinal outside its table reads as i = j = 0xffff: no LDS row)
-                    out[s * R + i] = ((uint64_t)d << 32) | (d < NB && t < pw ? pt[d * pw + t] : 0xffffffffu);
-            }
-            continue;
-        }
-        for (size_t i = 0; i < R; ++i) {
-            const uint32_t* q = &buf[i * sw + w];
-            if (m.compact[s] && q[0] == 0xffffffffu) // never written (SetDebug fill): no LDS row index is all-ones
-                out[s * R + i] = ~0ull;
-            else
-                out[s * R + i] = m.compact[s] ? ((uint64_t)cunpack_d(q[0], q[-1]) << 32) | (q[0] & m.cp_imask)
-                                              : ((uint64_t)q[1] << 32) | q[0];
-        }
-    }
-    return out;
-}
 size_t EquihashGpuSolver::DeviceBytes() const { return impl->bytes; }
 
+std::vector<std::vector<double>> EquihashGpuSolver::PhaseCycles(int nonces) {
+    return impl->with_cfg<std::vector<std::vector<double>>>([&](auto c) { return impl->phase_cycles<decltype(c)>(nonces); });
+}
+std::vector<uint32_t> EquihashGpuSolver::DebugFills(int nonce) {
+    return impl->with_cfg<std::vector<uint32_t>>([&](auto c) { return impl->debug_fills<decltype(c)>(nonce); });
+}
+std::vector<uint64_t> EquihashGpuSolver::DebugDump(int nonce) {
+    return impl->with_cfg<std::vector<uint64_t>>([&](auto c) { return impl->debug_dump<decltype(c)>(nonce); });
+}
 std::vector<uint32_t> EquihashGpuSolver::DebugExpandCorrupt(int mode) {
-    BCP_HIP_CHECK(hipSetDevice(impl->device));
-    BCP_HIP_CHECK(hipStreamSynchronize(impl->stream));
-    Impl& m = *impl;
-    uint32_t nc = 0;
-    BCP_HIP_CHECK(hipMemcpy(&nc, m.d_ncand.p, 4, hipMemcpyDeviceToHost));
-    nc = std::min<uint32_t>(nc, (uint32_t)m.maxcand);
-    if (nc == 0) return {};
-    uint64_t tri = 0;
-    BCP_HIP_CHECK(hipMemcpy(&tri, m.d_cand.p, 8, hipMemcpyDeviceToHost));
-    const size_t st = m.kstages - 1; // the stage the final round read
-    const uint32_t d = (uint32_t)(tri >> 32), i = (uint32_t)tri & 0xffff;
-    uint32_t* slot = m.d_rst[st].p + ((size_t)d * (m.rows / m.nb) + i) * m.slot_words[st] + m.row_words[st];
-    if (mode == 3 || mode == 4) {
-        // The table walk of a stage-(K-2) parent of the first candidate: mode 3 sets a padding bit
-        // above the producing bucket in its row (a bucket >= NB), mode 4 rewrites the run base of
-        // its (bucket, area) so that the slot's ordinal is the first one past the pair table.
-        if (st < 2 || !m.table[st - 1] || m.tp_mask[st - 1] < m.nb)
-            throw std::invalid_argument("DebugExpandCorrupt: modes 3 and 4 need table parents with spare padding in stage K-2");
-        uint32_t w[2] = {0, 0}; // the stage-(K-1) slot's parent word(s) -> its left parent (area d1, position i1)
-        BCP_HIP_CHECK(hipMemcpy(w, slot, m.compact[st] ? 4 : 8, hipMemcpyDeviceToHost));
-        uint32_t last = 0;
-        if (m.compact[st]) BCP_HIP_CHECK(hipMemcpy(&last, slot - 1, 4, hipMemcpyDeviceToHost));
-        const uint32_t d1 = m.compact[st] ? ((w[0] >> m.cp_ib) & m.cp_dhm) | (((w[0] >> (16 + m.cp_ib)) & m.cp_dhm) << m.cp_dh) |
-                                                ((last & m.cp_rmask) << m.cp_dx)
-                                          : w[1];
-        const uint32_t i1 = (m.compact[st] ? w[0] & m.cp_imask : w[0]) & 0xffff;
-        const size_t area = m.rows / m.nb;
-        if (d1 >= m.nb || i1 >= area) throw std::runtime_error("DebugExpandCorrupt: the first candidate's parent is out of range");
-        uint32_t* lw = m.d_rst[st - 1].p + ((size_t)d1 * area + i1) * m.slot_words[st - 1] + m.row_words[st - 1] - 1;
-        uint32_t x = 0;
-        BCP_HIP_CHECK(hipMemcpy(&x, lw, 4, hipMemcpyDeviceToHost));
-        if (mode == 3) {
-            x |= (uint32_t)m.nb;
-            BCP_HIP_CHECK(hipMemcpy(lw, &x, 4, hipMemcpyHostToDevice));
-        } else {
-            const uint32_t d2 = x & m.tp_mask[st - 1];
-            if (d2 >= m.nb) throw std::runtime_error("DebugExpandCorrupt: the parent row's bucket is out of range");
-            const uint32_t rb = i1 - (uint32_t)m.ptab_words[st - 1];
-            BCP_HIP_CHECK(hipMemcpy(m.d_btab[st - 1].p + (size_t)d2 * m.nb + d1, &rb, 4, hipMemcpyHostToDevice));
-        }
-    } else if (mode != 0) {
-        if (m.compact[st]) {
-            // compact word: i | j << 16 with the bucket's bits in the spare high bits of each half
-            uint32_t w = 0;
-            BCP_HIP_CHECK(hipMemcpy(&w, slot, 4, hipMemcpyDeviceToHost));
-            w = mode == 1 ? (w | (m.cp_dhm << m.cp_ib) | (m.cp_dhm << (16 + m.cp_ib))) : (w | ((1u << m.cp_ib) - 1));
-            BCP_HIP_CHECK(hipMemcpy(slot, &w, 4, hipMemcpyHostToDevice));
-        } else {
-            uint32_t w[2];
-            BCP_HIP_CHECK(hipMemcpy(w, slot, 8, hipMemcpyDeviceToHost));
-            if (mode == 1) w[1] = 0xffffu;         // producing bucket far past NB
-            else w[0] = (w[0] & 0xffff0000u) | 0xffffu; // LDS row far past the area
-            BCP_HIP_CHECK(hipMemcpy(slot, w, 8, hipMemcpyHostToDevice));
-        }
-    }
-    BCP_HIP_CHECK(hipMemsetAsync(m.d_nout.p, 0, 4, m.stream));
-    dispatch_cfg(m.n, m.k, [&](auto c) {
-        using C = decltype(c);
-        constexpr int EB = C::L < 64 ? 64 : C::L;
-        const bcpk::EhStages stages = m.stage_ptrs<C>();
-        hipLaunchKernelGGL((bcpk::eh_expand<C>), dim3(C::MAXCAND), dim3(EB), 0, m.stream, m.d_leaf.p, stages,
-                           m.d_ncand.p, m.d_cand.p, m.d_idx.p, m.d_valid.p, m.d_nout.p, m.d_out.p);
-    });
-    BCP_HIP_CHECK(hipGetLastError());
-    BCP_HIP_CHECK(hipStreamSynchronize(m.stream));
-    std::vector<uint32_t> valid(nc);
-    BCP_HIP_CHECK(hipMemcpy(valid.data(), m.d_valid.p, nc * 4, hipMemcpyDeviceToHost));
-    return valid;
+    return impl->with_cfg<std::vector<uint32_t>>([&](auto c) { return impl->debug_expand_corrupt<decltype(c)>(mode); });
 }
 
-void EquihashGpuSolver::Launch(const std::vector<EhBaseState>& states) {
-    if (states.empty() || (int)states.size() > impl->batch) throw std::invalid_argument("bad number of states");
-    if (impl->inflight) throw std::runtime_error("EquihashGpuSolver: Collect() the previous launch first");
-    BCP_HIP_CHECK(hipSetDevice(impl->device));
-    memcpy(impl->h_states.p, states.data(), states.size() * sizeof(EhBaseState));
-    dispatch_cfg(impl->n, impl->k, [&](auto c) { impl->launch<decltype(c)>(states.size()); });
-    impl->inflight = (int)states.size();
-}
-
+void EquihashGpuSolver::Launch(const std::vector<EhBaseState>& states) { impl->launch_states(states, nullptr); }
 void EquihashGpuSolver::Launch(const std::vector<EhBaseState>& states, const EquihashGpuSolver& prev) {
-    if (&prev == this) throw std::invalid_argument("EquihashGpuSolver: cannot pipeline behind itself");
-    if (prev.impl->device != impl->device) throw std::invalid_argument("EquihashGpuSolver: pipelined solvers on different devices");
-    impl->after = prev.impl.get();
-    try {
-        Launch(states);
-    } catch (...) {
-        impl->after = nullptr;
-        throw;
-    }
-    impl->after = nullptr;
+    impl->launch_states(states, impl->behind(prev));
 }
-
-void EquihashGpuSolver::LaunchPow(const EhPowJob& job) {
-    if (job.count < 1 || job.count > impl->batch) throw std::invalid_argument("LaunchPow: count must be 1..Batch()");
-    if (impl->inflight) throw std::runtime_error("EquihashGpuSolver: Collect() the previous launch first");
-    BCP_HIP_CHECK(hipSetDevice(impl->device));
-    bcpk::EhPowParams p;
-    static_assert(sizeof(p.prefix) == sizeof(job.prefix) && sizeof(p.nonce) == 32 && sizeof(p.target) == 32, "job words");
-    memcpy(p.prefix, job.prefix, sizeof(p.prefix));
-    memcpy(p.nonce, job.nonce_first, 32);
-    memcpy(p.target, job.target_le, 32);
-    impl->pow = &p;
-    try {
-        dispatch_cfg(impl->n, impl->k, [&](auto c) {
-            impl->alloc_pow<decltype(c)>();
-            impl->launch<decltype(c)>((size_t)job.count);
-        });
-    } catch (...) {
-        impl->pow = nullptr;
-        throw;
-    }
-    impl->pow = nullptr;
-    impl->pow_job = job;
-    impl->pow_inflight = true;
-    impl->inflight = job.count;
-}
-
+void EquihashGpuSolver::LaunchPow(const EhPowJob& job) { impl->launch_pow(job, nullptr); }
 void EquihashGpuSolver::LaunchPow(const EhPowJob& job, const EquihashGpuSolver& prev) {
-    if (&prev == this) throw std::invalid_argument("EquihashGpuSolver: cannot pipeline behind itself");
-    if (prev.impl->device != impl->device) throw std::invalid_argument("EquihashGpuSolver: pipelined solvers on different devices");
-    impl->after = prev.impl.get();
-    try {
-        LaunchPow(job);
-    } catch (...) {
-        impl->after = nullptr;
-        throw;
-    }
-    impl->after = nullptr;
+    impl->launch_pow(job, impl->behind(prev));
 }
 
 EhPowResult EquihashGpuSolver::CollectPow() {
     if (!impl->inflight) throw std::runtime_error("EquihashGpuSolver: nothing in flight");
     if (!impl->pow_inflight) throw std::runtime_error("EquihashGpuSolver: the launch in flight is a Launch(); use Collect()");
-    const int ns = impl->inflight;
-    impl->pow_collect = true;
-    Collect(); // the wait and the statistics; it decodes no index lists (they stayed on the device)
-    Impl& m = *impl;
-    const size_t nout = m.h_nout.p[0], nwin = m.h_powctr.p[0], ndup = m.h_powctr.p[1];
-    if (nwin > m.outq) // more winners than the per-batch copy holds: fetch the rest
-        BCP_HIP_CHECK(hipMemcpy(m.h_win.p + m.outq * m.winw, m.d_win.p + m.outq * m.winw,
-                                (nwin - m.outq) * m.winw * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    EhPowResult res;
-    res.solutions = nout - ndup;
-    m.stats.solutions += res.solutions;
-    const size_t solw = (m.winw - 11) * 4;
-    // the list is in completion order: by position in the nonce range, then by hash as an integer
-    std::vector<const uint32_t*> ents;
-    for (size_t e = 0; e < nwin; ++e) {
-        const uint32_t* p = m.h_win.p + e * m.winw;
-        if (p[0] < (uint32_t)ns) ents.push_back(p);
-    }
-    std::sort(ents.begin(), ents.end(), [](const uint32_t* a, const uint32_t* b) {
-        if (a[0] != b[0]) return a[0] < b[0];
-        for (int i = 7; i >= 0; --i)
-            if (a[3 + i] != b[3 + i]) return a[3 + i] < b[3 + i];
-        return a[1] < b[1];
-    });
-    for (const uint32_t* p : ents) {
-        EhPowHit h;
-        uint64_t carry = p[0];
-        for (int q = 0; q < 4; ++q) { // nonce_first + position, 256-bit little-endian
-            uint64_t a;
-            memcpy(&a, m.pow_job.nonce_first + 8 * q, 8);
-            const uint64_t s = a + carry;
-            carry = s < a ? 1 : 0;
-            memcpy(h.nonce + 8 * q, &s, 8);
-        }
-        memcpy(h.hash, p + 3, 32);
-        h.solution.assign(reinterpret_cast<const unsigned char*>(p + 11), reinterpret_cast<const unsigned char*>(p + 11) + solw);
-        if (m.debug) {
-            res.all.push_back(h);
-            res.all_pass.push_back(p[2] ? 1 : 0);
-        }
-        if (p[2]) res.hits.push_back(std::move(h));
-    }
-    return res;
+    return impl->with_cfg<EhPowResult>([&](auto c) { return impl->collect_pow<decltype(c)>(); });
 }
 
 std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Collect() {
     if (!impl->inflight) throw std::runtime_error("EquihashGpuSolver: nothing in flight");
-    const bool pow = impl->pow_collect; // called by CollectPow: the wait and the statistics only
-    if (impl->pow_inflight && !pow) throw std::runtime_error("EquihashGpuSolver: the launch in flight is a LaunchPow(); use CollectPow()");
-    impl->pow_collect = impl->pow_inflight = false;
-    BCP_HIP_CHECK(hipSetDevice(impl->device));
-    BCP_HIP_CHECK(hipStreamSynchronize(impl->stream));
-    const int ns = impl->inflight;
-    impl->inflight = 0;
-    float ms = 0;
-    BCP_HIP_CHECK(hipEventElapsedTime(&ms, impl->ev0, impl->ev1));
-    impl->stats.gpu_ms += ms;
-    impl->stats.nonces += ns;
-    {
-        // every nonce: pair-list drops per round and rows past a round's capacity per stage (accumulated)
-        const size_t K = impl->kstages;
-        impl->stats.pair_dropped_all.resize(K + 1, 0);
-        impl->stats.stage_dropped_all.resize(K, 0);
-        impl->stats.pair_dropped_nonce.assign(ns, 0);
-        impl->stats.stage_dropped_nonce.assign(ns, 0);
-        std::vector<uint64_t> pd(K + 1, 0);
-        for (int nn = 0; nn < ns; ++nn) {
-            const uint32_t* q = impl->h_pdrop.p + (size_t)nn * (2 * K + 2);
-            for (size_t r = 0; r <= K; ++r) {
-                pd[r] += q[r];
-                impl->stats.pair_dropped_all[r] += q[r];
-                impl->stats.pair_dropped_nonce[nn] += q[r];
-            }
-            for (size_t s = 0; s < K; ++s) {
-                impl->stats.stage_dropped_all[s] += q[K + 1 + s];
-                impl->stats.stage_dropped_nonce[nn] += q[K + 1 + s];
-            }
-        }
-        if (impl->debug) impl->stats.pair_dropped = pd;
-    }
-    if (impl->debug) {
-        // nonce 0: per stage, rows offered to each bucket (its fill counter) vs the LDS capacity
-        // of the round that reads it
-        const size_t NB = impl->nb;
-        impl->stats.stage_rows.assign(impl->kstages, 0);
-        impl->stats.stage_dropped.assign(impl->kstages, 0);
-        impl->stats.stage_maxfill.assign(impl->kstages, 0);
-        impl->stats.stage_top.assign(impl->kstages, {});
-        // every nonce of the batch: the fullest bucket per stage and the buckets past capacity
-        impl->stats.stage_maxfill_all.assign(impl->kstages, 0);
-        for (size_t s = 0; s < impl->kstages; ++s)
-            for (size_t x = 0; x < (size_t)ns * NB; ++x) {
-                const uint64_t fill = impl->h_ctr_all.p[(s * impl->batch) * NB + x];
-                impl->stats.stage_maxfill_all[s] = std::max<uint64_t>(impl->stats.stage_maxfill_all[s], fill);
-                if (fill > impl->caps[s]) impl->stats.overflow_fills.push_back((uint64_t)s << 32 | fill);
-            }
-        for (size_t s = 0; s < impl->kstages; ++s) {
-            std::vector<uint64_t> fills;
-            for (size_t dd = 0; dd < NB; ++dd) {
-                const uint64_t fill = impl->h_ctr0.p[s * NB + dd];
-                fills.push_back(fill);
-                impl->stats.stage_rows[s] += fill;
-                impl->stats.stage_maxfill[s] = std::max<uint64_t>(impl->stats.stage_maxfill[s], fill);
-                if (fill > impl->caps[s]) {
-                    impl->stats.stage_dropped[s] += fill - impl->caps[s];
-                    impl->stats.dropped_rows += fill - impl->caps[s];
-                }
-            }
-            std::sort(fills.rbegin(), fills.rend());
-            fills.resize(std::min<size_t>(fills.size(), 8));
-            impl->stats.stage_top[s] = fills;
-        }
-    }
-    std::vector<std::vector<std::vector<uint32_t>>> out(ns);
-    const size_t ew = impl->L + 2; // compact-list entry: nonce, candidate, L indices
-    const size_t nout = impl->h_nout.p[0];
-    if (!pow && nout > impl->outq) // more valid solutions than the per-batch copy holds: fetch the rest
-        BCP_HIP_CHECK(hipMemcpy(impl->h_out.p + impl->outq * ew, impl->d_out.p + impl->outq * ew,
-                                (nout - impl->outq) * ew * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (impl->debug) {
-        impl->stats.debug_cands.clear();
-        const uint32_t nc = std::min<uint32_t>(impl->h_ncand.p[0], (uint32_t)impl->maxcand);
-        for (uint32_t c = 0; c < nc; ++c) {
-            const uint32_t* p = impl->h_idx.p + (size_t)c * impl->L;
-            impl->stats.debug_cands.emplace_back(p, p + impl->L);
-        }
-    }
-    uint64_t cands = 0;
-    for (int nn = 0; nn < ns; ++nn) {
-        const uint32_t c = impl->h_ncand.p[nn];
-        cands += std::min<uint32_t>(c, (uint32_t)impl->maxcand);
-        impl->stats.cand_max = std::max<uint64_t>(impl->stats.cand_max, c);
-        if (c > impl->maxcand) impl->stats.cand_dropped += c - impl->maxcand; // lost candidates, maybe solutions
-    }
-    impl->stats.candidates += cands;
-    impl->stats.duplicates += cands - nout;
-    // the list is in completion order: put every nonce's solutions in candidate order
-    std::vector<std::pair<uint64_t, const uint32_t*>> ents;
-    ents.reserve(nout);
-    for (size_t e = 0; e < nout && !pow; ++e) {
-        const uint32_t* p = impl->h_out.p + e * ew;
-        if (p[0] < (uint32_t)ns) ents.emplace_back(((uint64_t)p[0] << 32) | p[1], p + 2);
-    }
-    std::sort(ents.begin(), ents.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    for (const auto& en : ents) {
-        const int nn = (int)(en.first >> 32);
-        std::vector<uint32_t> v(en.second, en.second + impl->L);
-        bool seen = false;
-        for (auto& prev : out[nn]) seen |= (prev == v);
-        if (seen) continue;
-        out[nn].push_back(std::move(v));
-        impl->stats.solutions++;
-    }
-    return out;
+    if (impl->pow_inflight) throw std::runtime_error("EquihashGpuSolver: the launch in flight is a LaunchPow(); use CollectPow()");
+    return impl->with_cfg<std::vector<std::vector<std::vector<uint32_t>>>>([&](auto c) { return impl->collect<decltype(c)>(); });
 }
 
 std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Solve(const std::vector<EhBaseState>& states) {
@@ -2178,3 +1882,4 @@ std::vector<std::vector<std::vector<uint32_t>>> EquihashGpuSolver::Solve(const s
 
 } // namespace gpu
 } // namespace bcp
+

@@ -347,3 +347,27 @@ def test_gpu_expand_rejects_out_of_range_parent(native, n, k):
     # and the device is fine afterwards: the same nonce solves to the same solutions
     # (the solver does not order a nonce's solutions: compare them as sets)
     assert [sorted(x) for x in solver.solve([st])] == [sorted(x) for x in first]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,k", [(96, 5), (200, 9)])
+def test_stamped_rounds_match_plain(native, n, k):
+    # The phase-stamped diagnostic round kernels (set_stamp_mode, read by tools/eh_diag.py and
+    # tools/eh_phases.py) solve like the plain ones, and phase_cycles reports one entry per round:
+    # [0] the whole bucket, [1..6] its phases, [7..8] the two halves of phase 4.
+    st = native.EquihashState(n, k)
+    st.update(header_input(0, b"main"))
+    solver = native.EquihashGpuSolver(n, k, 1)
+    plain = solver.solve([st])
+    solver.set_stamp_mode(True)
+    stamped = solver.solve([st])
+    assert [sorted(x) for x in stamped] == [sorted(x) for x in plain]
+    cycles = solver.phase_cycles(1)
+    assert len(cycles) == k
+    for stage, ph in enumerate(cycles):
+        print(stage + 1, [round(x) for x in ph])
+        assert len(ph) == 9
+        assert ph[0] > 0
+        # the phases lie inside the bucket (a phase the round does not have counts as 0); the means
+        # are sums of at most 2^9 integers below 2^40 in doubles: 1e-9 covers their rounding
+        assert ph[0] >= sum(ph[1:7]) * (1 - 1e-9), (stage + 1, ph)
