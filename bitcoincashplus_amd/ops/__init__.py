@@ -6,7 +6,7 @@ an explicit ``use_gpu=False``.
 
 Two input paths:
 * **Device-resident** (``torch.uint8`` tensors on the GPU): ``sha256d64``,
-  ``short_txids``, ``ecdsa_verify_compact`` and ``check_headers`` hand the tensors' device pointers to
+  ``short_txids``, ``bloom_match``, ``ecdsa_verify_compact`` and ``check_headers`` hand the tensors' device pointers to
   the kernels and enqueue them on the tensors' current torch stream
   (``torch.cuda.current_stream().cuda_stream``).  Results come back as GPU tensors;
   nothing is copied to the host and nothing synchronises, so the ops compose with
@@ -28,6 +28,8 @@ Kernel map (reference hot loops):
   ecdsa_verify       K8  batched secp256k1 verify                    secp256k1.hip
   verify_forkid      K8  block-path deferred checks -> verify batch  secp256k1.hip (GpuVerifyDeferred)
   short_txids        K9  BIP152 SipHash-2-4 short ids                relay.hip
+  bloom_match        K10 BIP37 filter membership (MurmurHash3 probes) relay.hip
+  bloom_scan         K10 a filter over a transaction list, exact     relay.hip + net/bloomscan.cpp
   Equihash solving (K1-K3) is ``models.EquihashModel.gpu_solver``.
 """
 from __future__ import annotations
@@ -214,7 +216,8 @@ def equihash_mine(n: int, k: int, prefix108, nonce_first, count: int, target, ba
 
 
 __all__ = ["sha256d64", "sha256d_batch", "merkle_root", "scan_nonces", "equihash_verify", "ecdsa_verify",
-           "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine", "check_headers"]
+           "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine", "check_headers",
+           "bloom_match", "bloom_scan"]
 
 
 def short_txids(k0: int, k1: int, txids, device: int = -1) -> list:
@@ -270,3 +273,52 @@ def verify_forkid(items: Iterable, use_gpu: bool = True):
     if use_gpu:
         require_gpu("verify_forkid")
     return native.verify_sig_deferred(list(items), use_gpu=use_gpu)
+
+
+def bloom_match(filter, n_hash: int, tweak: int, elements, device: int = -1):
+    """BIP37 membership (CBloomFilter::contains) of a batch of byte strings in the filter `filter`
+    (its vData, 1..36000 bytes) with `n_hash` hash functions (1..50) and tweak `tweak`.
+
+    Host path: `filter` is bytes and `elements` a list of non-empty byte strings; returns a list
+    of 0/1.
+
+    Device-resident path: `elements` is (blob, offs, lens): a ``torch.uint8`` GPU tensor of element
+    bytes at any address, and int32 GPU tensors [n] with each element's offset into it and its
+    length; `filter` is bytes or a uint8 GPU tensor. The kernel is enqueued on the current torch
+    stream and the result is a [n] uint8 GPU tensor: 1 / 0, and 2 for an element that is empty or
+    reaches past the blob (the kernel reads nothing of it)."""
+    require_gpu("bloom_match")
+    if isinstance(elements, tuple) and len(elements) == 3 and _on_gpu(elements[0]):
+        blob, offs, lens = elements
+        blob = _u8(blob, "bloom_match").view(-1)
+        if not (_on_gpu(offs) and _on_gpu(lens) and offs.dtype == lens.dtype == torch.int32):
+            raise TypeError("bloom_match: offs and lens are torch.int32 GPU tensors")
+        offs, lens = offs.detach().contiguous().view(-1), lens.detach().contiguous().view(-1)
+        if _on_gpu(filter):
+            f = _u8(filter, "bloom_match").view(-1)
+        else:
+            raw = _as_bytes(filter)
+            if not raw:
+                raise ValueError("bloom_match: empty filter")
+            f = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(blob.device)
+        nf = f.numel()
+        n = offs.numel()
+        if lens.numel() != n or not (blob.device == offs.device == lens.device == f.device):
+            raise ValueError("bloom_match: offs and lens are [n]; all tensors on one device")
+        out = torch.empty(n, dtype=torch.uint8, device=blob.device)
+        dev, stream = _dev_stream(blob)
+        native.bloom_match_device(f.data_ptr(), nf, n_hash, tweak, blob.data_ptr(), blob.numel(), offs.data_ptr(),
+                                  lens.data_ptr(), out.data_ptr(), n, dev, stream)
+        return out
+    return native.bloom_match_gpu(_as_bytes(filter), n_hash, tweak, [bytes(e) for e in elements], device)
+
+
+def bloom_scan(txs, filter_ser, use_gpu: bool = True):
+    """A peer's filter over a list of serialized transactions, equal to CBloomFilter::
+    IsRelevantAndUpdate on each in turn (inserts under BLOOM_UPDATE_ALL / P2PUBKEY_ONLY included),
+    with the membership tests batched on the device. `filter_ser` is a ``filterload`` payload.
+    Returns ([bool], the filter's payload afterwards, info) with info = {elements, rounds,
+    cpu_reruns, used_gpu}. ``use_gpu=False`` runs the same batched scan on the CPU."""
+    if use_gpu:
+        require_gpu("bloom_scan")
+    return native.bloom_scan([bytes(t) for t in txs], bytes(filter_ser), use_gpu)

@@ -61,7 +61,9 @@ void CBloomFilter::insert(const std::vector<unsigned char>& vKey) {
     if (isFull || vData.empty()) return;
     for (unsigned i = 0; i < nHashFuncs; i++) {
         const unsigned nIndex = Hash(i, vKey);
-        vData[nIndex >> 3] |= (1 << (7 & nIndex));
+        const unsigned char bit = 1 << (7 & nIndex);
+        if (!(vData[nIndex >> 3] & bit)) nBitsFlipped++;
+        vData[nIndex >> 3] |= bit;
     }
     isEmpty = false;
 }
@@ -286,6 +288,17 @@ CMerkleBlock::CMerkleBlock(const CBlock& block, CBloomFilter& filter) {
         } else {
             vMatch.push_back(false);
         }
+        vHashes.push_back(hash);
+    }
+    txn = CPartialMerkleTree(vHashes, vMatch);
+}
+
+CMerkleBlock::CMerkleBlock(const CBlock& block, const std::vector<bool>& vMatch) {
+    header = block.GetBlockHeader();
+    std::vector<uint256> vHashes;
+    for (unsigned i = 0; i < block.vtx.size(); i++) {
+        const uint256& hash = block.vtx[i]->GetHash();
+        if (vMatch[i]) vMatchedTxn.push_back(std::make_pair(i, hash));
         vHashes.push_back(hash);
     }
     txn = CPartialMerkleTree(vHashes, vMatch);

@@ -32,6 +32,15 @@ public:
     bool IsWithinSizeConstraints() const;
     bool IsRelevantAndUpdate(const CTransaction& tx);
     void UpdateEmptyFull();
+    // What a batched scan (net/bloomscan.h) needs to see: the raw parameters, the shortcut
+    // states, and how many bits insert() has flipped so far (no result depends on the count).
+    const std::vector<unsigned char>& Data() const { return vData; }
+    unsigned HashFuncs() const { return nHashFuncs; }
+    unsigned Tweak() const { return nTweak; }
+    unsigned char Flags() const { return nFlags; }
+    bool IsFull() const { return isFull; }
+    bool IsEmpty() const { return isEmpty; }
+    uint64_t BitsFlipped() const { return nBitsFlipped; }
     template <typename S> void Serialize(S& s) const {
         ::bcp::Serialize(s, vData);
         ::bcp::Serialize(s, nHashFuncs);
@@ -53,6 +62,7 @@ private:
     bool isFull, isEmpty;
     unsigned nHashFuncs, nTweak;
     unsigned char nFlags;
+    uint64_t nBitsFlipped = 0;
 };
 
 // Probabilistic "recently seen" set with bounded memory (three generations).
@@ -116,6 +126,9 @@ public:
     CMerkleBlock() {}
     CMerkleBlock(const CBlock& block, CBloomFilter& filter);
     CMerkleBlock(const CBlock& block, const std::set<uint256>& txids);
+    // From verdicts computed beforehand (vMatch[i] = the filter's IsRelevantAndUpdate of vtx[i],
+    // the filter already updated): the first constructor without its scan.
+    CMerkleBlock(const CBlock& block, const std::vector<bool>& vMatch);
     template <typename S> void Serialize(S& s) const {
         ::bcp::Serialize(s, header);
         ::bcp::Serialize(s, txn);

@@ -198,6 +198,45 @@ int64_t Sha256dScanNonces(const unsigned char header80[80], const unsigned char 
 std::vector<uint64_t> ShortTxIdBatch(uint64_t k0, uint64_t k1, const unsigned char* txids32, size_t n,
                                      int device = -1);
 
+// --------------------------------------------------------------- relay: BIP37 bloom filters
+// CBloomFilter::contains for a batch of byte strings (reference src/bloom.cpp:82-91): element i is
+// blob[offs[i] .. offs[i] + lens[i]), filter = vData (1..36000 bytes), nHashFuncs 1..50.
+// match[i] = 1 iff every probe MurmurHash3(h * 0xFBA4C795 + nTweak, element) % (filterBytes * 8),
+// h < nHashFuncs, finds its bit set. Both forms throw std::invalid_argument on an empty or
+// oversized filter, on a hash function count outside 1..50 and (the host forms) on an empty
+// element or one that reaches past the blob.
+//
+// The element table (blob, offsets, lengths; pinned staging and its device copy) is an object of
+// its own, so that a second filter over the same elements costs only the filter's upload and the
+// kernel. One thread drives a table at a time; tables of one device share the relay stream.
+class BloomElementTable {
+public:
+    explicit BloomElementTable(int device = -1);
+    ~BloomElementTable();
+    BloomElementTable(const BloomElementTable&) = delete;
+    BloomElementTable& operator=(const BloomElementTable&) = delete;
+    int Device() const;
+    // Pinned staging for n elements and blobBytes of element data, to be written by the caller
+    // (threads may write disjoint parts). Discards the table staged before.
+    void Stage(size_t n, size_t blobBytes, uint32_t** offs, uint32_t** lens, unsigned char** blob);
+    // Checks every staged (offset, length) against the blob; throws and leaves the table unusable
+    // if one fails. The upload rides on the first Match.
+    void Commit();
+    size_t Size() const; // committed elements
+    // match[i - first] = contains(element i) for first <= i < Size(): one H2D copy (filter and,
+    // the first time, the table), one launch, one D2H copy, then a wait.
+    void Match(const unsigned char* filter, uint32_t filterBytes, uint32_t nHashFuncs, uint32_t nTweak, size_t first,
+               uint8_t* match);
+    struct Impl;
+
+private:
+    std::unique_ptr<Impl> impl;
+};
+// From host memory through a per-device table of the relay context.
+void BloomMatchBatch(const unsigned char* filter, uint32_t filterBytes, uint32_t nHashFuncs, uint32_t nTweak,
+                     const unsigned char* blob, size_t blobBytes, const uint32_t* offs, const uint32_t* lens, size_t n,
+                     std::vector<uint8_t>& match, int device = -1);
+
 // --------------------------------------------------------------- secp256k1
 // ECDSA verification batch: N jobs, msg32 = N*32 (big-endian digest bytes as signed),
 // sig64 = N*64 (r||s big-endian, s low-S-normalised, r,s in [1,n-1] checked on host),
@@ -231,6 +270,13 @@ int EcdsaSplitKernel();
 void Sha256d64Device(const void* in64, void* out32, size_t n, int device, uintptr_t stream);
 // out[i] = BIP152 short id of txid i (48 bits in a uint64); txids32 16-byte aligned
 void ShortTxIdsDevice(uint64_t k0, uint64_t k1, const void* txids32, void* out64, size_t n, int device,
+                      uintptr_t stream);
+// BloomMatchBatch on device memory: filter, blob, offs (uint32, 4-byte aligned), lens (the same)
+// and match (n bytes) are device pointers of any other alignment. The element ranges cannot be
+// checked here: the kernel reads nothing of an empty element or one that reaches past blobBytes
+// and writes 2 for it.
+void BloomMatchDevice(const void* filter, uint32_t filterBytes, uint32_t nHashFuncs, uint32_t nTweak, const void* blob,
+                      size_t blobBytes, const void* offs, const void* lens, void* match, size_t n, int device,
                       uintptr_t stream);
 // Device scratch the ECDSA kernels need per signature (the prep kernel's job records).
 size_t EcdsaJobBytes();

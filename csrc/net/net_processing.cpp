@@ -2,6 +2,7 @@
 #include "consensus/merkleblock.h"
 #include "consensus/tx_verify.h"
 #include "net/blockencodings.h"
+#include "net/bloomscan.h"
 #include "node/policy.h"
 #include "node/txmempool.h"
 #include "node/validation.h"
@@ -669,7 +670,12 @@ void PeerLogicValidation::Impl::ProcessGetData(CNode* pfrom, std::deque<CInv>& v
                         std::lock_guard<std::mutex> lf(pfrom->cs_filter);
                         if (pfrom->pfilter) {
                             sendMerkle = true;
-                            merkleBlock = CMerkleBlock(*pblock, *pfrom->pfilter);
+                            // a large block goes through the batched scan (membership tests on
+                            // the device); verdicts and filter equal the per-transaction loop's
+                            if (GpuBloomScanWanted(pblock->vtx.size()))
+                                merkleBlock = CMerkleBlock(*pblock, BloomScanTransactions(pblock->vtx, *pfrom->pfilter, true));
+                            else
+                                merkleBlock = CMerkleBlock(*pblock, *pfrom->pfilter);
                         }
                     }
                     if (sendMerkle) {
@@ -1903,11 +1909,26 @@ bool PeerLogicValidation::SendMessages(CNode* pto, std::atomic<bool>& interrupt)
             pto->fSendMempool = false;
             const Amount filterrate = pto->minFeeFilter;
             std::lock_guard<std::mutex> lf(pto->cs_filter);
-            for (const TxMempoolInfo& txinfo : I.pool->infoAll()) {
+            const std::vector<TxMempoolInfo> vtxinfo = I.pool->infoAll();
+            // under a filter a large pool is scanned as one list (the entries the fee filter
+            // lets through, in this order): the loop below then reads the verdicts
+            std::vector<bool> verdicts;
+            bool scanned = false;
+            if (pto->pfilter && GpuBloomScanWanted(vtxinfo.size())) {
+                std::vector<CTransactionRef> passing;
+                for (const TxMempoolInfo& txinfo : vtxinfo)
+                    if (!(filterrate && txinfo.feeRate.GetFeePerK() < filterrate)) passing.push_back(txinfo.tx);
+                verdicts = BloomScanTransactions(passing, *pto->pfilter, true);
+                scanned = true;
+            }
+            size_t nPassing = 0;
+            for (const TxMempoolInfo& txinfo : vtxinfo) {
                 const uint256& h = txinfo.tx->GetHash();
                 pto->setInventoryTxToSend.erase(h);
                 if (filterrate && txinfo.feeRate.GetFeePerK() < filterrate) continue;
-                if (pto->pfilter && !pto->pfilter->IsRelevantAndUpdate(*txinfo.tx)) continue;
+                if (scanned) {
+                    if (!verdicts[nPassing++]) continue;
+                } else if (pto->pfilter && !pto->pfilter->IsRelevantAndUpdate(*txinfo.tx)) continue;
                 pto->filterInventoryKnown.insert(h);
                 vInv.push_back(CInv(MSG_TX, h));
                 if (vInv.size() == MAX_INV_SZ) {

@@ -22,6 +22,7 @@ template <class A> inline pyb::bytes to_bytes(const std::vector<unsigned char, A
 void bind_crypto(pyb::module_& m);
 void bind_equihash(pyb::module_& m);
 void bind_gpu(pyb::module_& m);
+void bind_bloom(pyb::module_& m);
 void bind_consensus(pyb::module_& m);
 void bind_script(pyb::module_& m);
 void bind_node(pyb::module_& m);

@@ -9,6 +9,7 @@
 #include "node/sigverify.h"
 #include "node/txmempool.h"
 #include "rpc/core_io.h"
+#include "net/bloomscan.h"
 #include "net/net.h"
 #include "rpc/server.h"
 #include "script/sign.h"
@@ -119,6 +120,17 @@ static UniValue getgpuinfo(const JSONRPCRequest& req) {
     sv.pushKV("gpu_failures", (uint64_t)s.gpu_failures);
     sv.pushKV("gpu_disabled", GpuSigPathDisabled());
     obj.pushKV("sigverify", sv);
+    // BIP37 filter scans of whole blocks and the pool (net/bloomscan.h)
+    const BloomScanStats bs = GetBloomScanStats();
+    UniValue bl(UniValue::VOBJ);
+    bl.pushKV("gpu_scans", bs.gpu_scans);
+    bl.pushKV("gpu_elements", bs.gpu_elements);
+    bl.pushKV("rounds", bs.rounds);
+    bl.pushKV("cpu_reruns", bs.cpu_reruns);
+    bl.pushKV("cpu_scans", bs.cpu_scans);
+    bl.pushKV("gpu_failures", bs.gpu_failures);
+    bl.pushKV("threshold", (uint64_t)GetGpuBloomThreshold());
+    obj.pushKV("bloom", bl);
     // validation lanes (node/gpuverify.h): devices, stream priority, work done per lane
     GpuVerifyService& svc = GpuVerifyService::Instance();
     UniValue vd(UniValue::VARR);

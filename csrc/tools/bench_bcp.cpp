@@ -27,6 +27,7 @@
 #include "secp256k1/secp256k1.h"
 #include "node/txmempool.h"
 #include "node/validation.h"
+#include "net/bloomscan.h"
 #include "primitives/block.h"
 #include "util/lockedpool.h"
 #include "util/strencodings.h"
@@ -39,6 +40,7 @@
 #include <cstdio>
 #include <fstream>
 #include <functional>
+#include <random>
 #include <regex>
 #include <thread>
 
@@ -1462,6 +1464,83 @@ static void Headers2000_ProcessNewBlockHeaders(State& st) {
     }
 }
 BENCHMARK(Headers2000_ProcessNewBlockHeaders);
+
+// A peer's BIP37 filter over a whole block or the pool: the per-transaction loop of
+// CBloomFilter::IsRelevantAndUpdate (what getdata MSG_FILTERED_BLOCK and the mempool reply do
+// below -gpubloomthreshold) against the batched scan with its membership passes on the device
+// (net/bloomscan.h), alternating run by run in this process. Lists of 2-in/2-out P2PKH
+// transactions as in the 8 MB connect block (9 elements each); the filter is sized for 1,000
+// elements at fp 0.0001 and watches 100 of the list's key hashes. The arms must agree on every
+// verdict and on the filter afterwards.
+static void BloomScanBench(State& st, const char* what, size_t ntx, unsigned char flags) {
+    if (!gpu::GpuAvailable()) return;
+    std::mt19937_64 rng(ntx * 4 + flags);
+    auto bytes = [&](size_t n) {
+        std::vector<unsigned char> v(n);
+        for (auto& c : v) c = (unsigned char)rng();
+        return v;
+    };
+    std::vector<CTransactionRef> txs;
+    std::vector<std::vector<unsigned char>> keyHashes;
+    for (size_t t = 0; t < ntx; t++) {
+        CMutableTransaction m;
+        for (int k = 0; k < 2; k++) {
+            m.vin.emplace_back();
+            uint256 h;
+            for (int j = 0; j < 32; j++) h.begin()[j] = (unsigned char)rng();
+            m.vin.back().prevout = COutPoint(h, (uint32_t)(rng() % 1750));
+            std::vector<unsigned char> pub = bytes(33);
+            pub[0] = 0x02 | (pub[0] & 1);
+            m.vin.back().scriptSig = CScript() << bytes(71 + rng() % 2) << pub;
+            keyHashes.push_back(bytes(20));
+            m.vout.push_back(CTxOut(50000, CScript() << OP_DUP << OP_HASH160 << keyHashes.back() << OP_EQUALVERIFY << OP_CHECKSIG));
+        }
+        txs.push_back(MakeTransactionRef(std::move(m)));
+    }
+    CBloomFilter loaded(1000, 0.0001, 0x5bd1e995, flags);
+    for (size_t i = 0; i < 100; i++) loaded.insert(keyHashes[i * keyHashes.size() / 100]);
+    std::vector<double> ms[2];
+    std::vector<bool> verdicts[2];
+    std::vector<unsigned char> after[2];
+    BloomScanInfo info;
+    int iters = 0;
+    while (st.KeepRunning()) {
+        const int arm = iters % 2;
+        CBloomFilter f = loaded;
+        const int64_t t0 = GetTimeMicros();
+        if (arm == 0) {
+            verdicts[0].assign(ntx, false);
+            for (size_t t = 0; t < ntx; t++) verdicts[0][t] = f.IsRelevantAndUpdate(*txs[t]);
+        } else {
+            verdicts[1] = BloomScanTransactions(txs, f, true, &info);
+            if (!info.usedGpu) throw std::runtime_error("bench: the bloom scan did not run on the device");
+        }
+        const int64_t t1 = GetTimeMicros();
+        after[arm] = SerializeToBytes(f);
+        if (iters >= 1 && (verdicts[0] != verdicts[1] || after[0] != after[1]))
+            throw std::runtime_error("bench: the bloom arms disagree");
+        if (iters >= 2) ms[arm].push_back((t1 - t0) / 1000.0); // each arm's first run grows buffers
+        iters++;
+    }
+    const size_t matched = std::count(verdicts[0].begin(), verdicts[0].end(), true);
+    for (int arm = 0; arm < 2; arm++) {
+        std::vector<double>& v = ms[arm];
+        if (v.empty()) continue;
+        std::sort(v.begin(), v.end());
+        printf("# bloom %s flags=%d %s: runs %zu, median %.3f ms (min %.3f, max %.3f), %zu txs, %zu matched", what, (int)flags,
+               arm ? "gpu" : "cpu", v.size(), v[v.size() / 2], v.front(), v.back(), ntx, matched);
+        if (arm) printf(", %zu elements, %zu rounds, %zu cpu reruns", info.elements, info.rounds, info.cpuReruns);
+        printf("\n");
+    }
+}
+static bench::Reg reg_Bloom1kNone("Bloom_Block1k_UpdateNone", [](State& st) { BloomScanBench(st, "block1k", 1000, BLOOM_UPDATE_NONE); });
+static bench::Reg reg_Bloom1kAll("Bloom_Block1k_UpdateAll", [](State& st) { BloomScanBench(st, "block1k", 1000, BLOOM_UPDATE_ALL); });
+static bench::Reg reg_Bloom4kNone("Bloom_Block4k_UpdateNone", [](State& st) { BloomScanBench(st, "block4k", 4000, BLOOM_UPDATE_NONE); });
+static bench::Reg reg_Bloom4kAll("Bloom_Block4k_UpdateAll", [](State& st) { BloomScanBench(st, "block4k", 4000, BLOOM_UPDATE_ALL); });
+static bench::Reg reg_Bloom21kNone("Bloom_Block21k_UpdateNone", [](State& st) { BloomScanBench(st, "block21k", 21000, BLOOM_UPDATE_NONE); });
+static bench::Reg reg_Bloom21kAll("Bloom_Block21k_UpdateAll", [](State& st) { BloomScanBench(st, "block21k", 21000, BLOOM_UPDATE_ALL); });
+static bench::Reg reg_Bloom100kNone("Bloom_Mempool100k_UpdateNone", [](State& st) { BloomScanBench(st, "mempool100k", 100000, BLOOM_UPDATE_NONE); });
+static bench::Reg reg_Bloom100kAll("Bloom_Mempool100k_UpdateAll", [](State& st) { BloomScanBench(st, "mempool100k", 100000, BLOOM_UPDATE_ALL); });
 
 int main(int argc, char* argv[]) {
     gArgs.ParseParameters(argc, argv);
