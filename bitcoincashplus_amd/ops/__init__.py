@@ -6,7 +6,7 @@ an explicit ``use_gpu=False``.
 
 Two input paths:
 * **Device-resident** (``torch.uint8`` tensors on the GPU): ``sha256d64``,
-  ``short_txids``, ``bloom_match``, ``ecdsa_verify_compact`` and ``check_headers`` hand the tensors' device pointers to
+  ``short_txids``, ``bloom_match``, ``hash160``, ``wallet_match``, ``ecdsa_verify_compact`` and ``check_headers`` hand the tensors' device pointers to
   the kernels and enqueue them on the tensors' current torch stream
   (``torch.cuda.current_stream().cuda_stream``).  Results come back as GPU tensors;
   nothing is copied to the host and nothing synchronises, so the ops compose with
@@ -30,6 +30,9 @@ Kernel map (reference hot loops):
   short_txids        K9  BIP152 SipHash-2-4 short ids                relay.hip
   bloom_match        K10 BIP37 filter membership (MurmurHash3 probes) relay.hip
   bloom_scan         K10 a filter over a transaction list, exact     relay.hip + net/bloomscan.cpp
+  hash160            K11 RIPEMD160(SHA256(m)) of byte strings         wallet_match.hip
+  wallet_match       K12 txids, prevouts, scripts against the wallet's match table  wallet_match.hip
+  wallet_scan        K12 a transaction list against a wallet, exact  wallet_match.hip + wallet/walletscan.cpp
   Equihash solving (K1-K3) is ``models.EquihashModel.gpu_solver``.
 """
 from __future__ import annotations
@@ -217,7 +220,7 @@ def equihash_mine(n: int, k: int, prefix108, nonce_first, count: int, target, ba
 
 __all__ = ["sha256d64", "sha256d_batch", "merkle_root", "scan_nonces", "equihash_verify", "ecdsa_verify",
            "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine", "check_headers",
-           "bloom_match", "bloom_scan"]
+           "bloom_match", "bloom_scan", "hash160", "wallet_match", "wallet_scan"]
 
 
 def short_txids(k0: int, k1: int, txids, device: int = -1) -> list:
@@ -322,3 +325,81 @@ def bloom_scan(txs, filter_ser, use_gpu: bool = True):
     if use_gpu:
         require_gpu("bloom_scan")
     return native.bloom_scan([bytes(t) for t in txs], bytes(filter_ser), use_gpu)
+
+
+def _packed_tensors(what, blob, offs, lens):
+    blob = _u8(blob, what).view(-1)
+    if not (_on_gpu(offs) and _on_gpu(lens) and offs.dtype == lens.dtype == torch.int32):
+        raise TypeError(f"{what}: offs and lens are torch.int32 GPU tensors")
+    offs, lens = offs.detach().contiguous().view(-1), lens.detach().contiguous().view(-1)
+    if lens.numel() != offs.numel() or not (blob.device == offs.device == lens.device):
+        raise ValueError(f"{what}: offs and lens are [n]; all tensors on one device")
+    return blob, offs, lens
+
+
+def hash160(messages, device: int = -1):
+    """RIPEMD160(SHA256(m)) of a batch of byte strings of 0..520 bytes (CHash160).
+
+    Host path: a list of byte strings; returns a list of 20-byte digests.
+
+    Device-resident path: `messages` is (blob, offs, lens) as in ``bloom_match``. The kernel is
+    enqueued on the current torch stream and the result is (digests [n, 20] uint8, status [n]
+    uint8) on the GPU: status 1, or 2 for a message that is longer than 520 bytes or reaches past
+    the blob (the kernel reads nothing of it and its digest is zero)."""
+    require_gpu("hash160")
+    if isinstance(messages, tuple) and len(messages) == 3 and _on_gpu(messages[0]):
+        blob, offs, lens = _packed_tensors("hash160", *messages)
+        n = offs.numel()
+        out = torch.empty((n, 20), dtype=torch.uint8, device=blob.device)
+        status = torch.empty(n, dtype=torch.uint8, device=blob.device)
+        dev, stream = _dev_stream(blob)
+        native.hash160_device(blob.data_ptr(), blob.numel(), offs.data_ptr(), lens.data_ptr(), out.data_ptr(),
+                              status.data_ptr(), n, dev, stream)
+        return out, status
+    return native.hash160_gpu([bytes(m) for m in messages], device)
+
+
+def wallet_match(table_desc: dict, items, device: int = -1, kind_mask: int = 7):
+    """Which of `items` can concern a wallet: each item against the match table of `table_desc` =
+    {salt (16 bytes, optional), keys (20-byte ids), watch (scripts), txids, spent (36-byte
+    outpoints)}. An item is (kind, bytes) with kind ``native.WM_ITEM_TXID`` / ``_INPUT`` /
+    ``_OUTPUT``; the result is a flag byte per item (``native.WM_HIT_K`` / ``_W`` / ``_T`` / ``_S``
+    bits, ``native.WM_NOT_READ`` for an item the kernel did not read), equal to
+    ``native.wallet_match_cpu``, false positives of the fingerprints included.
+
+    Host path: `items` is a list of (kind, bytes); returns a list of ints.
+
+    Device-resident path: `items` is (kinds, blob, offs, lens): uint8 GPU tensors of kinds [n] and
+    of item bytes at any address, int32 GPU tensors [n] of offsets and lengths. The table is built
+    on the host and uploaded; the kernel is enqueued on the current torch stream and the result
+    is a [n] uint8 GPU tensor."""
+    require_gpu("wallet_match")
+    if isinstance(items, tuple) and len(items) == 4 and _on_gpu(items[0]):
+        kinds = _u8(items[0], "wallet_match").view(-1)
+        blob, offs, lens = _packed_tensors("wallet_match", *items[1:])
+        n = offs.numel()
+        if kinds.numel() != n or kinds.device != blob.device:
+            raise ValueError("wallet_match: kinds is [n] on the items' device")
+        t = native.wallet_match_table(table_desc)
+        slots = torch.frombuffer(bytearray(t["slots"]), dtype=torch.int64).to(blob.device)
+        out = torch.empty(n, dtype=torch.uint8, device=blob.device)
+        dev, stream = _dev_stream(blob)
+        native.wallet_match_device(slots.data_ptr(), t["n_slots"], t["k0"], t["k1"], t["has_watch"], kind_mask,
+                                   kinds.data_ptr(), blob.data_ptr(), blob.numel(), offs.data_ptr(), lens.data_ptr(),
+                                   out.data_ptr(), n, dev, stream)
+        slots.record_stream(torch.cuda.current_stream(dev))
+        return out
+    return native.wallet_match_gpu(table_desc, [(int(k), bytes(b)) for k, b in items], device)
+
+
+def wallet_scan(txs, wallet_desc: dict, use_gpu: bool = True, f_update: bool = True):
+    """A list of serialized transactions against a wallet, equal to
+    CWallet::AddToWalletIfInvolvingMe on each in turn, with the membership tests batched on the
+    device. `wallet_desc` = {pubkeys, scripts (redeem scripts), watch (watch-only scripts),
+    wallet_txs (serialized transactions already in the wallet)}. Returns ([bool], the wallet's
+    transactions as txid || hashBlock || nIndex, its spent outpoints as outpoint || spender, info)
+    with info = {items, passes, cpu_reruns, used_gpu}. ``use_gpu=False`` runs the same batched
+    scan on the CPU."""
+    if use_gpu:
+        require_gpu("wallet_scan")
+    return native.wallet_scan([bytes(t) for t in txs], wallet_desc, use_gpu, f_update)

@@ -237,6 +237,56 @@ void BloomMatchBatch(const unsigned char* filter, uint32_t filterBytes, uint32_t
                      const unsigned char* blob, size_t blobBytes, const uint32_t* offs, const uint32_t* lens, size_t n,
                      std::vector<uint8_t>& match, int device = -1);
 
+// --------------------------------------------------------------- relay: wallet matching
+// out[20 * i ..] = RIPEMD160(SHA256(blob[offs[i] .. offs[i] + lens[i]))), messages of 0..520 bytes
+// (CHash160). Throws std::invalid_argument on a longer message or one that reaches past the blob.
+std::vector<unsigned char> Hash160Batch(const unsigned char* blob, size_t blobBytes, const uint32_t* offs,
+                                        const uint32_t* lens, size_t n, int device = -1);
+
+// A wallet match table as kernels/wallet_match.h defines it (built by bcp::WalletMatchTable,
+// csrc/wallet/walletmatch.h): nSlots 64-bit entries, a power of two, under the salt (k0, k1).
+struct WalletMatchTableDesc {
+    const uint64_t* slots;
+    uint32_t nSlots;
+    uint64_t k0, k1;
+    bool hasWatch; // the table holds watch-only script entries: outputs probe them
+};
+// The items of one transaction list (kind, offset, length into one blob; pinned staging and its
+// device copy) and up to two tables they are matched against: 0, the wallet's table, and 1, a
+// small table of what a scan added. A later pass over the same items costs a table upload (or a
+// few patched slots) and the kernel. One thread drives an object at a time; all share the relay
+// stream of their device.
+class WalletMatchItems {
+public:
+    explicit WalletMatchItems(int device = -1);
+    ~WalletMatchItems();
+    WalletMatchItems(const WalletMatchItems&) = delete;
+    WalletMatchItems& operator=(const WalletMatchItems&) = delete;
+    int Device() const;
+    // Pinned staging for n items and blobBytes of item data, to be written by the caller (threads
+    // may write disjoint parts). Discards the items staged before.
+    void Stage(size_t n, size_t blobBytes, uint8_t** kinds, uint32_t** offs, uint32_t** lens, unsigned char** blob);
+    // Checks every staged kind and (offset, length); throws and leaves the items unusable if one
+    // fails. The upload rides on the first Match.
+    void Commit();
+    size_t Size() const; // committed items
+    // Copies the table into pinned memory; the upload rides on the next Match against it.
+    void SetTable(int which, const WalletMatchTableDesc& table);
+    // The table set before, with the listed slots changed (an append that did not grow it): only
+    // those are uploaded, or all of it past 64 of them.
+    void PatchTable(int which, const uint32_t* slotIdx, size_t n, const WalletMatchTableDesc& table);
+    // flags[i - first] = the wm::Flag bits of item i for first <= i < Size(); items whose kind is
+    // not in kindMask get 0. Pending uploads, one launch, one D2H copy, then a wait.
+    void Match(int which, size_t first, uint32_t kindMask, uint8_t* flags);
+    struct Impl;
+
+private:
+    std::unique_ptr<Impl> impl;
+};
+// From host memory through a per-device WalletMatchItems of the relay context, every kind.
+void WalletMatchBatch(const WalletMatchTableDesc& table, const uint8_t* kinds, const unsigned char* blob, size_t blobBytes,
+                      const uint32_t* offs, const uint32_t* lens, size_t n, std::vector<uint8_t>& flags, int device = -1);
+
 // --------------------------------------------------------------- secp256k1
 // ECDSA verification batch: N jobs, msg32 = N*32 (big-endian digest bytes as signed),
 // sig64 = N*64 (r||s big-endian, s low-S-normalised, r,s in [1,n-1] checked on host),
@@ -278,6 +328,17 @@ void ShortTxIdsDevice(uint64_t k0, uint64_t k1, const void* txids32, void* out64
 void BloomMatchDevice(const void* filter, uint32_t filterBytes, uint32_t nHashFuncs, uint32_t nTweak, const void* blob,
                       size_t blobBytes, const void* offs, const void* lens, void* match, size_t n, int device,
                       uintptr_t stream);
+// Hash160Batch on device memory: out20 = n x 20 bytes, status = n bytes (1, or 2 for a message
+// longer than 520 bytes or reaching past blobBytes: nothing of it is read, its 20 bytes are zero).
+// offs and lens are 4-byte aligned, everything else of any alignment.
+void Hash160Device(const void* blob, size_t blobBytes, const void* offs, const void* lens, void* out20, void* status,
+                   size_t n, int device, uintptr_t stream);
+// WalletMatchBatch on device memory: slots 8-byte aligned, offs and lens 4-byte aligned, kinds,
+// blob and flags (n bytes) of any alignment. An item that reaches past blobBytes is not read and
+// gets wm::NOT_READ.
+void WalletMatchDevice(const void* slots, uint32_t nSlots, uint64_t k0, uint64_t k1, bool hasWatch, uint32_t kindMask,
+                       const void* kinds, const void* blob, size_t blobBytes, const void* offs, const void* lens,
+                       void* flags, size_t n, int device, uintptr_t stream);
 // Device scratch the ECDSA kernels need per signature (the prep kernel's job records).
 size_t EcdsaJobBytes();
 // result[i] = 1 iff signature i verifies; inputs as EcdsaVerifyBatch (msg32 n x 32, sig64 compact

@@ -12,6 +12,7 @@
 
 #include "kernels/gpu_api.h"
 #include "kernels/hip_util.h"
+#include "kernels/relay_ctx.h"
 
 #include <algorithm>
 #include <cstring>
@@ -148,26 +149,6 @@ __global__ __launch_bounds__(256) void bloom_match_kernel(const uint8_t* __restr
 
 namespace bcp {
 namespace gpu {
-
-namespace {
-// Per-device stream and grow-only pinned/device staging of the relay entry points; calls on
-// one device are serialised by its mutex.
-struct RelayCtx {
-    std::mutex m;
-    hipStream_t s = nullptr;
-    LaneState st; // staging slots only (the stream above is the one used)
-};
-RelayCtx& Ctx(int device) {
-    static RelayCtx ctx[64];
-    if (device < 0 || device >= 64) throw std::runtime_error("relay GPU context: device index out of range");
-    return ctx[device];
-}
-std::unique_lock<std::mutex> Lock(RelayCtx& c) {
-    std::unique_lock<std::mutex> l(c.m);
-    if (!c.s) BCP_HIP_CHECK(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
-    return l;
-}
-} // namespace
 
 std::vector<uint64_t> ShortTxIdBatch(uint64_t k0, uint64_t k1, const unsigned char* txids32, size_t n, int device) {
     std::vector<uint64_t> out(n);

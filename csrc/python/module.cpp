@@ -8,6 +8,7 @@ PYBIND11_MODULE(_bcpnative, m) {
     bcp::py::bind_equihash(m);
     bcp::py::bind_gpu(m);
     bcp::py::bind_bloom(m);
+    bcp::py::bind_walletscan(m);
     bcp::py::bind_consensus(m);
     bcp::py::bind_script(m);
     bcp::py::bind_node(m);

@@ -19,6 +19,7 @@
 #include "node/miner.h"
 #include "util/lockedpool.h"
 #include "util/strencodings.h"
+#include "wallet/walletscan.h"
 
 #include <mutex>
 
@@ -131,6 +132,17 @@ static UniValue getgpuinfo(const JSONRPCRequest& req) {
     bl.pushKV("gpu_failures", bs.gpu_failures);
     bl.pushKV("threshold", (uint64_t)GetGpuBloomThreshold());
     obj.pushKV("bloom", bl);
+    // wallet scans of whole blocks (wallet/walletscan.h)
+    const WalletScanStats ws = GetWalletScanStats();
+    UniValue wl(UniValue::VOBJ);
+    wl.pushKV("wallet_scans", ws.wallet_scans);
+    wl.pushKV("items", ws.items);
+    wl.pushKV("passes", ws.passes);
+    wl.pushKV("cpu_reruns", ws.cpu_reruns);
+    wl.pushKV("cpu_scans", ws.cpu_scans);
+    wl.pushKV("gpu_failures", ws.gpu_failures);
+    wl.pushKV("threshold", (uint64_t)GetGpuWalletScanThreshold());
+    obj.pushKV("walletscan", wl);
     // validation lanes (node/gpuverify.h): devices, stream priority, work done per lane
     GpuVerifyService& svc = GpuVerifyService::Instance();
     UniValue vd(UniValue::VARR);

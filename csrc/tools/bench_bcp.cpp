@@ -33,6 +33,7 @@
 #include "util/strencodings.h"
 #include "util/util.h"
 #include "wallet/wallet.h"
+#include "wallet/walletscan.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1541,6 +1542,108 @@ static bench::Reg reg_Bloom21kNone("Bloom_Block21k_UpdateNone", [](State& st) { 
 static bench::Reg reg_Bloom21kAll("Bloom_Block21k_UpdateAll", [](State& st) { BloomScanBench(st, "block21k", 21000, BLOOM_UPDATE_ALL); });
 static bench::Reg reg_Bloom100kNone("Bloom_Mempool100k_UpdateNone", [](State& st) { BloomScanBench(st, "mempool100k", 100000, BLOOM_UPDATE_NONE); });
 static bench::Reg reg_Bloom100kAll("Bloom_Mempool100k_UpdateAll", [](State& st) { BloomScanBench(st, "mempool100k", 100000, BLOOM_UPDATE_ALL); });
+
+// The wallet over a whole block: the per-transaction loop of CWallet::AddToWalletIfInvolvingMe
+// (what a rescan and BlockConnected do below -gpuwalletscanthreshold) against the batched scan
+// with its match passes on the device (wallet/walletscan.h), alternating run by run in this
+// process, over the 2-in/2-out P2PKH list of the 8 MB connect block (5 items each). Every run
+// gets a fresh memory-only wallet of `nkeys` keys, so `owned` transactions are found anew each
+// time; filling it, and for the scan arm a one-transaction scan that builds and uploads the match
+// table (once per rescan, not per block), are not timed. The arms must agree on every verdict.
+static void WalletScanBench(State& st, const char* what, size_t ntx, size_t nkeys, size_t owned) {
+    if (!gpu::GpuAvailable()) return;
+    std::mt19937_64 rng(ntx * 8 + nkeys + owned);
+    auto bytes = [&](size_t n) {
+        std::vector<unsigned char> v(n);
+        for (auto& c : v) c = (unsigned char)rng();
+        return v;
+    };
+    std::vector<CPubKey> keys;
+    for (size_t k = 0; k < nkeys; k++) {
+        std::vector<unsigned char> pub = bytes(33);
+        pub[0] = 0x02 | (pub[0] & 1); // IsMine hashes a key and never checks the point
+        keys.push_back(CPubKey(pub.begin(), pub.end()));
+    }
+    std::vector<CTransactionRef> txs;
+    for (size_t t = 0; t < ntx; t++) {
+        CMutableTransaction m;
+        const bool ours = owned && t % (ntx / owned) == ntx / owned / 2 && t / (ntx / owned) < owned;
+        for (int k = 0; k < 2; k++) {
+            m.vin.emplace_back();
+            uint256 h;
+            for (int j = 0; j < 32; j++) h.begin()[j] = (unsigned char)rng();
+            m.vin.back().prevout = COutPoint(h, (uint32_t)(rng() % 1750));
+            std::vector<unsigned char> pub = bytes(33);
+            pub[0] = 0x02 | (pub[0] & 1);
+            m.vin.back().scriptSig = CScript() << bytes(71 + rng() % 2) << pub;
+            std::vector<unsigned char> kh = bytes(20);
+            if (ours && k == 0) {
+                const CKeyID id = keys[rng() % nkeys].GetID();
+                kh.assign(id.begin(), id.end());
+            }
+            m.vout.push_back(CTxOut(50000, CScript() << OP_DUP << OP_HASH160 << kh << OP_EQUALVERIFY << OP_CHECKSIG));
+        }
+        txs.push_back(MakeTransactionRef(std::move(m)));
+    }
+    const std::vector<CTransactionRef> primer{txs[0]};
+    static const uint256 blockHash = uint256S("00000000000000000000000000000000000000000000000000000000000b10c0");
+    CBlockIndex index;
+    index.phashBlock = &blockHash;
+    CKey dummy;
+    dummy.MakeNewKey(true);
+    std::vector<double> ms[2], extractMs, matchMs, walkMs;
+    std::vector<bool> verdicts[2];
+    WalletScanInfo info;
+    int iters = 0;
+    while (st.KeepRunning()) {
+        const int arm = iters % 2;
+        CWallet w{"bench", "", true};
+        for (const CPubKey& p : keys) w.LoadKey(dummy, p);
+        if (arm == 1) WalletScanTransactions(w, primer, &index, true, true);
+        const int64_t t0 = GetTimeMicros();
+        if (arm == 0) {
+            verdicts[0].assign(ntx, false);
+            for (size_t t = 0; t < ntx; t++) verdicts[0][t] = w.AddToWalletIfInvolvingMe(txs[t], &index, (int)t, true);
+        } else {
+            verdicts[1] = WalletScanTransactions(w, txs, &index, true, true, &info);
+            if (!info.usedGpu) throw std::runtime_error("bench: the wallet scan did not run on the device");
+        }
+        const int64_t t1 = GetTimeMicros();
+        if (iters >= 1 && verdicts[0] != verdicts[1]) throw std::runtime_error("bench: the wallet scan arms disagree");
+        if (iters >= 2) { // each arm's first run grows buffers
+            ms[arm].push_back((t1 - t0) / 1000.0);
+            if (arm) {
+                extractMs.push_back(info.extractMicros / 1000.0);
+                matchMs.push_back(info.matchMicros / 1000.0);
+                walkMs.push_back(info.walkMicros / 1000.0);
+            }
+        }
+        iters++;
+    }
+    const size_t found = std::count(verdicts[0].begin(), verdicts[0].end(), true);
+    auto median = [](std::vector<double> v) {
+        std::sort(v.begin(), v.end());
+        return v.empty() ? 0.0 : v[v.size() / 2];
+    };
+    for (int arm = 0; arm < 2; arm++) {
+        std::vector<double>& v = ms[arm];
+        if (v.empty()) continue;
+        std::sort(v.begin(), v.end());
+        printf("# walletscan %s keys=%zu owned=%zu %s: runs %zu, median %.3f ms (min %.3f, max %.3f), %zu txs, %zu found", what,
+               nkeys, owned, arm ? "gpu" : "loop", v.size(), v[v.size() / 2], v.front(), v.back(), ntx, found);
+        if (arm)
+            printf(", %zu items, %zu passes, %zu cpu reruns; medians: extract %.3f ms, match passes %.3f ms, walk %.3f ms",
+                   info.items, info.passes, info.cpuReruns, median(extractMs), median(matchMs), median(walkMs));
+        printf("\n");
+    }
+}
+static bench::Reg reg_Wallet21k_1k_0("WalletScan_Block21k_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block21k", 21000, 1000, 0); });
+static bench::Reg reg_Wallet21k_1k_100("WalletScan_Block21k_Keys1k_Owned100", [](State& st) { WalletScanBench(st, "block21k", 21000, 1000, 100); });
+static bench::Reg reg_Wallet21k_100k_0("WalletScan_Block21k_Keys100k_Owned0", [](State& st) { WalletScanBench(st, "block21k", 21000, 100000, 0); });
+static bench::Reg reg_Wallet21k_100k_100("WalletScan_Block21k_Keys100k_Owned100", [](State& st) { WalletScanBench(st, "block21k", 21000, 100000, 100); });
+static bench::Reg reg_Wallet1k_1k_0("WalletScan_Block1k_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block1k", 1000, 1000, 0); });
+static bench::Reg reg_Wallet4k_1k_0("WalletScan_Block4k_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block4k", 4000, 1000, 0); });
+static bench::Reg reg_Wallet250_1k_0("WalletScan_Block250_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block250", 250, 1000, 0); });
 
 int main(int argc, char* argv[]) {
     gArgs.ParseParameters(argc, argv);

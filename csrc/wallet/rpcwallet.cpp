@@ -1445,6 +1445,7 @@ static UniValue removeprunedfunds(const JSONRPCRequest& req) {
         else ++o;
     }
     w.mapWallet.erase(it);
+    w.InvalidateScanCache();
     w.DB().Erase(std::make_pair(std::string("tx"), h), true);
     return UniValue::NullUniValue;
 }

@@ -10,6 +10,7 @@
 #include "script/sign.h"
 #include "util/strencodings.h"
 #include "util/util.h"
+#include "wallet/walletscan.h"
 
 #include <algorithm>
 #include <limits>
@@ -526,6 +527,7 @@ bool CWallet::AddWatchOnly(const CScript& dest, int64_t nCreateTime) {
 bool CWallet::RemoveWatchOnly(const CScript& dest) {
     WalletLock l(*this);
     if (!CBasicKeyStore::RemoveWatchOnly(dest)) return false;
+    InvalidateScanCache();
     KVBatch b;
     b.Erase(K("watchs", dest));
     b.Erase(K("watchmeta", dest));
@@ -821,6 +823,7 @@ bool CWallet::AddToWallet(const CWalletTx& wtxIn, bool) {
             if (pi) wtx.nTimeSmart = (uint32_t)std::min<int64_t>(pi->GetBlockTime(), wtx.nTimeReceived);
         }
         AddToSpends(hash);
+        NoteScanCacheAdded(*wtx.tx);
     } else {
         if (!wtxIn.hashBlock.IsNull() && wtxIn.hashBlock != wtx.hashBlock) {
             wtx.hashBlock = wtxIn.hashBlock;
@@ -936,6 +939,10 @@ void CWallet::BlockConnected(const std::shared_ptr<const CBlock>& block, const C
                              const std::vector<CTransactionRef>& conflicted) {
     WalletLock l(*this);
     for (const CTransactionRef& t : conflicted) SyncTransaction(t);
+    if (GpuWalletScanWanted(block->vtx.size())) {
+        WalletScanTransactions(*this, block->vtx, pindex, true, true); // SyncTransaction of each, as one batch
+        return;
+    }
     for (size_t i = 0; i < block->vtx.size(); i++) SyncTransaction(block->vtx[i], pindex, (int)i);
 }
 
@@ -1008,8 +1015,13 @@ bool CWallet::ScanForWalletTransactions(const CBlockIndex* pindex, bool fUpdate,
             std::lock_guard<CCriticalSection> lm(chainstate->cs());
             if (!chainstate->ReadBlock(block, pindex, false)) break;
             WalletLock l(*this);
-            for (size_t i = 0; i < block.vtx.size(); i++)
-                if (AddToWalletIfInvolvingMe(block.vtx[i], pindex, (int)i, fUpdate)) found++;
+            if (GpuWalletScanWanted(block.vtx.size())) {
+                // the whole block as one batch (wallet/walletscan.h): the same verdicts and wallet
+                for (bool added : WalletScanTransactions(*this, block.vtx, pindex, fUpdate, true)) found += added;
+            } else {
+                for (size_t i = 0; i < block.vtx.size(); i++)
+                    if (AddToWalletIfInvolvingMe(block.vtx[i], pindex, (int)i, fUpdate)) found++;
+            }
             pindex = chainstate->ActiveChain().Next(pindex);
         }
     }

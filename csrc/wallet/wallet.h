@@ -33,6 +33,7 @@ namespace bcp {
 class Chainstate;
 class CTxMemPool;
 class CWallet;
+struct WalletScanCache;
 
 static const unsigned int DEFAULT_KEYPOOL_SIZE = 100;
 static const Amount DEFAULT_TRANSACTION_FEE = 0;
@@ -357,6 +358,11 @@ public:
     // them, and writes back what moved (reference CWallet::ReorderTransactions, run by
     // LoadWallet when any record is unordered).
     bool ReorderTransactions();
+    // Call after removing a member of mapWallet, mapTxSpends or the keystore by hand: the next
+    // scan then rebuilds its match table (wallet/walletscan.h). Additions need no call.
+    void InvalidateScanCache();
+    void NoteScanCacheAdded(const CTransaction& tx); // AddToWallet's new entry, appended to that table
+    const std::multimap<COutPoint, uint256>& TxSpends() const { return mapTxSpends; } // under cs_wallet
 
     // ---- ownership / amounts
     isminetype IsMine(const CTxIn& txin) const;
@@ -454,6 +460,9 @@ private:
     std::set<int64_t> setKeyPool;
     std::set<COutPoint> setLockedCoins;
     std::multimap<COutPoint, uint256> mapTxSpends;
+    // the match table of wallet/walletscan.cpp, kept between scans (guarded by cs_wallet)
+    std::shared_ptr<WalletScanCache> scanCache;
+    friend struct WalletScanAccess;
     int64_t nNextResend = 0;
     int64_t nLastResend = 0;
     uint64_t nAccountingEntryNumber = 0;

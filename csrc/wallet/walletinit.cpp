@@ -120,6 +120,7 @@ static bool LoadOneWallet(NodeContext& node, const std::string& name, std::strin
         w->DB().WriteBatch(b, true);
         w->mapWallet.clear();
         w->wtxOrdered.clear();
+        w->InvalidateScanCache();
     }
     w->Attach(&cs, node.mempool.get());
     if (gArgs.IsArgSet("-paytxfee")) {

@@ -26,7 +26,7 @@
 #                        of the 160k-sigop GPU connect
 #   ibd TAG [BLOCKS] [SECS]  IBD runs, plus interleaved A/Bs of -connectlookahead and -connectinplace:
 #                            per-run ms/block, median/min/max per configuration, phase split
-#   relay TAG            BIP152 short-id kernel: GPU tests and the CPU vs GPU micro-bench
+#   relay TAG            BIP152 short-id kernel: GPU tests and the CPU vs GPU micro-bench; the wallet scan bench cases
 #   lanes TAG            verify-service tests, then a 199k-signature and a 2000-header batch over
 #                        lanes [0], [0,0], [0,0,0,0] (sharding overhead) and the host-built-state
 #                        header path, with a kernel trace of the 2000-header runs
@@ -182,7 +182,10 @@ relay)
     > "$O/pytest.log" 2>&1
   tail -n 3 "$O/pytest.log"
   timeout -k 10 120 ./bin/bench_bcp -filter='(CPU|GPU)_ShortIds.*' -time=2 > "$O/micro.log" 2>&1
-  cat "$O/micro.log" ;;
+  cat "$O/micro.log"
+  # the wallet over a 21k-transaction block: the loop against the batched scan (profiles/wallet_scan.md)
+  timeout -k 10 300 ./bin/bench_bcp -filter='WalletScan_.*' -time=4 > "$O/wallet_scan.log" 2>&1
+  grep '^# walletscan' "$O/wallet_scan.log" ;;
 lanes)
   timeout -k 10 400 python -u -m pytest tests/test_gpu_verify_service.py -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$O/pytest.log" 2>&1 || { tail -n 30 "$O/pytest.log"; exit 1; }
