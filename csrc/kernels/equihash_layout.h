@@ -51,12 +51,22 @@
 #define BCP_EH_TABLE_PARENTS 1 //    tables beside the slot array (EhCfg::tp); 0: every slot carries its parent word(s)
 #endif
 
+#ifndef BCP_EH_KEY_SLOTS // slots per key of a "slot round" (EhCfg::ks): the commit files each row's id under its key,
+#define BCP_EH_KEY_SLOTS 8 //   which replaces the key sort. 8 (one 16-byte LDS read per key) or 0: every round sorts
+#endif
+#ifndef BCP_EH_OVL // slot rounds: entries of the overflow list (rows of rank >= BCP_EH_KEY_SLOTS in their key group).
+#define BCP_EH_OVL 128 //   The fullest bucket of the bench's 20 default steps held 16 (profiles/equihash_r10.md)
+#endif
+static_assert(BCP_EH_KEY_SLOTS == 0 || BCP_EH_KEY_SLOTS == 8, "a key's slots are one 16-byte LDS read");
+static_assert(BCP_EH_OVL >= 1 && BCP_EH_OVL <= 128, "the overflow list is walked by the first BCP_EH_OVL lanes");
+
 namespace bcpk {
 
 // (defined with the round kernels' geometry below; EhCfg's table-parent layout follows from them)
 template <class C> constexpr int round_nt(int stage, bool carry);
 template <class C> constexpr int round_mp(int stage, bool carry = false);
 template <class C> constexpr bool round_prunes(int stage, bool carry = false);
+template <class C> constexpr bool slot_round_fits(int stage);
 
 // N, K: Equihash parameters. BB: bucket bits. CAP/CAP4/CAP3: LDS row capacity of rounds reading
 // rows of >= 5, 4, <= 3 words. NT: threads per round workgroup; WGCU: round workgroups per CU
@@ -146,6 +156,20 @@ struct EhCfg {
         return stage == 0 || tp(stage) ? words(stage) : words(stage) + (cp(stage) ? 1 : 2);
     }
     static constexpr size_t ROWS = (size_t)NB * AREA; // slots per stage per nonce
+    // Slot rounds: ks(stage) > 0 when the collision round producing `stage` keeps, instead of the
+    // key sort, a table of ks row ids per key filled at the commit (slot_lds below). Such a round
+    // needs a key space worth the table (>= 256 keys: (48,5) has 32) and the table next to its
+    // rows in LDS, plain and carrying: (200,9) rounds 3..8 (1 and 2 would take ~174 KB), every collision
+    // round of (96,5). The final round keeps the sort.
+    static constexpr int ks(int stage) {
+        return BCP_EH_KEY_SLOTS && stage >= 1 && stage < K && NRESTS >= 256 && slot_round_fits<EhCfg>(stage)
+                   ? BCP_EH_KEY_SLOTS
+                   : 0;
+    }
+    // Counters per nonce (pdrop): [1..K] pairs dropped per round, [K+1..2K] rows dropped per
+    // stage; with slot rounds also [2K+2..3K+1] overflow rows per round (2K+1+round) and
+    // [3K+2..4K+1] the most overflow rows one bucket of the round had (3K+1+round).
+    static constexpr int PDW = 2 * K + 2 + (BCP_EH_KEY_SLOTS ? 2 * K : 0);
     // 16-bit LDS histograms (two counters per word) where 32-bit ones would not fit two per CU
     static constexpr bool H16 = NB > 512;
     static constexpr int HW = H16 ? NB / 2 : NB;      // words per histogram
@@ -232,11 +256,39 @@ template <class C> constexpr int round_lds(int stage, bool prune, bool carry = f
     return (cap * WI + 3) / 4 * 16 + pruneb + 4 + round_un<C>(stage, carry) + hists +
            (round_nt<C>(stage, carry) / 64 + 1) * 4 + gen;
 }
+// A slot round (EhCfg::ks). Its union `un` (bytes): {ktab[NRESTS][8] u16, the row ids of each key
+// by rank (never cleared: reads are bounded by the key's count); bend[NRESTS] u32, the key counts;
+// ovl[BCP_EH_OVL] u32, (key << 16 | row) of the rows of rank >= 8; the pair list plist[MP*NT] u32}
+// during the collision search, spair aliasing plist after it. Beside `un` one more word, the
+// overflow list's fill. round_lds, round_un and un_walk_* keep describing the sorted round.
+template <class C> constexpr int un_slot_bend() { return C::NRESTS * 8 * 2; }
+template <class C> constexpr int un_slot_ovl() { return un_slot_bend<C>() + C::NRESTS * 4; }
+template <class C> constexpr int un_slot_list() { return un_slot_ovl<C>() + BCP_EH_OVL * 4; }
+template <class C> constexpr int slot_un(int stage, bool carry = false) {
+    return un_slot_list<C>() + round_mp<C>(stage, carry) * round_nt<C>(stage, carry) * 4;
+}
+template <class C> constexpr int slot_lds(int stage, bool prune, bool carry = false) {
+    const int b = round_lds<C>(stage, prune, carry) - round_un<C>(stage, carry) + slot_un<C>(stage, carry) + 4;
+    return carry ? (b + 7) / 8 * 8 : b; // (the generation waves' 8-byte round-0 prefix words come last)
+}
+// Workgroup barriers of one bucket iteration, by round variant: the count and the barrier that
+// ends the pair listing, the pair filter, the first of the destination scan's two, the pair sort
+// (the emit ends with the last one). The sorted round has three more before the listing: the key
+// scan's two and the key placement's. eh_round and eh_carry_gen both take them from here.
+struct EhBars {
+    int n, list, filter, scan, sort;
+};
+constexpr EhBars eh_bars(bool slot) { return slot ? EhBars{7, 2, 3, 4, 6} : EhBars{10, 5, 6, 7, 9}; }
 // Depth-1 duplicate pruning wherever its parent words fit next to the full rows.
 template <class C> constexpr bool round_prunes(int stage, bool carry) {
     // (the pruning start was measured on (200,9); the small configurations keep pruning from round 2)
     constexpr int from = C::K == 9 ? BCP_EH_PRUNE_FROM : 2;
     return (stage >= from || stage == C::K) && stage >= 2 && round_lds<C>(stage, true, carry) <= C::LDS_BUDGET;
+}
+
+template <class C> constexpr bool slot_round_fits(int stage) {
+    return slot_lds<C>(stage, round_prunes<C>(stage, false), false) <= C::LDS_BUDGET &&
+           (C::GW == 0 || slot_lds<C>(stage, round_prunes<C>(stage, true), true) <= C::LDS_BUDGET);
 }
 
 // Generation carried by the collision rounds of the previous nonce group. The (K-1)*NB bucket

@@ -16,8 +16,15 @@
 //    known so its latency hides behind the scan and scatter), and writes its rows into the
 //    claimed runs. The consumer round then reads its bucket as one contiguous block (16-byte
 //    loads, straight into LDS): no run tables, slot maps or per-row gather maps.
-//  * Collisions on the remaining RB = DB-BB bits of the digit are found by a counting sort of
-//    the bucket on those bits and an atomic-free pair enumeration (scan + max-scan); each output
+//  * Collisions on the remaining RB = DB-BB bits of the digit (the key) are found by grouping the
+//    bucket's rows by key and listing the pairs of every group. The commit takes each row's rank
+//    in its key group with a returning LDS atomic. A sorted round ((200,9) rounds 1-2, (48,5),
+//    every final round) then scans the key counts and places the row ids in key order; a slot
+//    round (EhCfg::ks: (200,9) rounds 3-8, (96,5)) needs no order: the commit writes the row's id
+//    into slot `rank` of its key's 8 slots, a row later reads all its partners with one 16-byte
+//    LDS load, and the few rows of rank >= 8 (about one per bucket) go through an overflow list.
+//    That takes the key scan, the placement pass and three of ten barriers out of the bucket
+//    iteration (profiles/equihash_r10.md). Each output
 //    row keeps a parent triple (producing bucket, LDS row i, LDS row j; in its slot or, see Memory
 //    layout, in the producing bucket's tables), so nothing ever carries
 //    index lists: the parents of a stage-s row are the stage-(s-1) slots bucket*AREA + i and
@@ -61,6 +68,15 @@
 #endif
 #ifndef BCP_EH_PF_SLICES // the next bucket's rows are prefetched in this many slices
 #define BCP_EH_PF_SLICES 3
+#endif
+#ifndef BCP_EH_SLOT_LIST // slot rounds, how a row writes out the pairs with its key's slots: 1 = a short loop with a
+#define BCP_EH_SLOT_LIST 1 //   register select; 0 = eight predicated stores, fully unrolled: 0.7% fewer Sol/s and 300-700
+#endif                     //   more cycles per bucket (profiles/equihash_r10.md)
+#ifndef BCP_EH_SLOT_RB // generation waves of a carrying slot round: the BLAKE2b round at which the slice of the
+#define BCP_EH_SLOT_RB 5 //   commit interval stops, and (BCP_EH_SLOT_RD) the slice of the pair-listing interval
+#endif
+#ifndef BCP_EH_SLOT_RD
+#define BCP_EH_SLOT_RD 10
 #endif
 #ifndef BCP_EH_GROUPS_DEFAULT // nonce groups of a solver by its batch size (BCP_EH_GROUPS overrides at run time):
 #define BCP_EH_GROUPS_DEFAULT(batch) ((batch) >= 48 ? (batch) / 24 : 1) // groups of 24 nonces; measured at 96 (profiles/equihash_r7.md)
@@ -442,24 +458,24 @@ struct EhCarry {
 };
 
 // Workgroup barrier k of a carrying round's bucket iteration. The round waves and the generation
-// waves run different code between the SAME number of barriers: each path executes eh_bar<1> ..
-// eh_bar<EH_NBAR> exactly once per bucket, in order, and one prologue barrier before the loop. The two
-// barriers inside block_exscan are written out at its call sites as EH_BAR_SCAN(k) (a check
-// only; block_exscan executes them).
-constexpr int EH_NBAR = 10;
+// waves run different code between the SAME number of barriers: each path executes eh_bar<1, NBAR> ..
+// eh_bar<NBAR, NBAR> exactly once per bucket, in order, and one prologue barrier before the loop.
+// NBAR = eh_bars(slot round).n (equihash_layout.h) on either path: 10 in a sorted round, 7 in a
+// slot round. No barrier depends on data. The two barriers inside block_exscan are written out at
+// its call sites as EH_BAR_SCAN(k, NBAR) (a check only; block_exscan executes them).
 constexpr int EH_SCAN_BARS = 2; // block_exscan with more than one wave
-template <int K> __device__ __forceinline__ void eh_bar() {
-    static_assert(K >= 1 && K <= EH_NBAR, "barrier outside the bucket iteration's count");
+template <int K, int NBAR> __device__ __forceinline__ void eh_bar() {
+    static_assert(K >= 1 && K <= NBAR, "barrier outside the bucket iteration's count");
     __syncthreads();
 }
-#define EH_BAR_SCAN(k) static_assert((k) >= 1 && (k) + EH_SCAN_BARS - 1 <= EH_NBAR, "scan barriers")
+#define EH_BAR_SCAN(k, nbar) static_assert((k) >= 1 && (k) + EH_SCAN_BARS - 1 <= (nbar), "scan barriers")
 
 // The generation waves of a carrying round (threads C::RNT.. of the workgroup). They walk the
 // same buckets as the round waves (the same xcd_bucket sequence, so the same trip count) and in
 // bucket (nonce n, d) generate chunk (STAGE-1)*NB + d of the next group's nonce n: what eh_gen_reg
 // does for a workgroup's rows, cut into slices between the round's barriers. The slices follow
 // the length of the round waves' intervals (profiles/equihash_r6.md, per-bucket cycles), so that
-// the generation waves are not the last to reach a barrier —
+// the generation waves are not the last to reach a barrier (barrier numbers of a sorted round) —
 //   before barrier 1 (commit), 4 (key placement), 5 (pair listing), 6 (pair filter): BLAKE2b
 //   rounds; nothing inside the round's two block scans (barriers 2, 3 and 7, 8 are a few hundred
 //   cycles apart); before 5 also one lane's round-0 prefix when the next bucket is another nonce's;
@@ -471,6 +487,9 @@ template <int K> __device__ __forceinline__ void eh_bar() {
 //   before 9: run bases to LDS;
 //   before 10 (emit, the round's longest interval): the rows and their leaf indices go to the
 //   claimed runs, then the NEXT bucket's hashes start (the state words stay in registers).
+// A slot round (EhCfg::ks) has no key scan and no key placement: its barriers 2..7 are the sorted
+// round's 5..10, the slices keep their intervals, and the BLAKE2b round of the key-placement
+// interval runs in the pair-listing interval (BCP_EH_SLOT_RB .. BCP_EH_SLOT_RD).
 // A bucket whose partner nonce does not exist or whose chunk lies past the nonce's last hash
 // only keeps the barriers.
 template <class C, int STAGE>
@@ -499,7 +518,11 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
     // BLAKE2b round at which each slice stops (round 0 belongs to begin())
     // in the round's emit / commit / key placement / pair listing interval; the pair filter
     // interval takes the rest (the schedules measured are in profiles/equihash_r7.md)
-    constexpr int RA = 3, RB = 5, RC = 6, RD = 10;
+    constexpr bool SLOT = C::ks(STAGE) > 0;
+    constexpr EhBars BAR = eh_bars(SLOT);
+    constexpr int NBAR = BAR.n;
+    constexpr int RA = 3, RB = SLOT ? BCP_EH_SLOT_RB : 5, RC = SLOT ? RB : 6, RD = SLOT ? BCP_EH_SLOT_RD : 10;
+    static_assert(RA <= RB && RB <= RC && RC <= RD && RD <= 12, "BLAKE2b slices in order");
     EhHdrHash hs[HB];
     // start the hashes of bucket b's chunk: begin() and rounds 1..RA-1
     auto start = [&](int b) {
@@ -536,22 +559,24 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 #pragma unroll
             for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RA, RB>(bs);
         }
-        eh_bar<1>();
-        eh_bar<2>(); // (the round waves are inside their key scan: two short intervals)
-        eh_bar<3>();
-        if (act) {
+        eh_bar<1, NBAR>();
+        if constexpr (!SLOT) {
+            eh_bar<2, NBAR>(); // (the round waves are inside their key scan: two short intervals)
+            eh_bar<3, NBAR>();
+            if (act) {
 #pragma unroll
-            for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RB, RC>(bs);
+                for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RB, RC>(bs);
+            }
+            eh_bar<4, NBAR>();
         }
-        eh_bar<4>();
         if (act) {
 #pragma unroll
             for (int hh = 0; hh < HB; ++hh) hs[hh].template rounds<RC, RD>(bs);
         }
         // the next bucket's prefix, when its nonce is another one: gr0p is read only in start()
-        // (before barrier 10 of the previous bucket; next after barrier 9 of this one)
+        // (before the last barrier of the previous bucket; next after the pair-sort barrier of this one)
         if (more && bn / C::NB != nonce) prefix(bn);
-        eh_bar<5>();
+        eh_bar<BAR.list, NBAR>();
         if (act) {
 #pragma unroll
             for (int hh = 0; hh < HB; ++hh) {
@@ -581,7 +606,7 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
                 }
             }
         }
-        eh_bar<6>();
+        eh_bar<BAR.filter, NBAR>();
         if (act) {
 #pragma unroll
             for (int k = 0; k < GC::BPT; ++k) {
@@ -591,10 +616,10 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
                 if (c) myb[k] = atomicAdd(&cy.CTR0[(size_t)nonce * C::NB + b], c);
             }
         }
-        eh_bar<7>();
+        eh_bar<BAR.scan, NBAR>();
         if (act)
             for (int i = gtid; i < C::NB; i += GT) ghist[i] = 0;
-        eh_bar<8>();
+        eh_bar<BAR.scan + 1, NBAR>();
         if (act) {
 #pragma unroll
             for (int k = 0; k < GC::BPT; ++k) {
@@ -602,7 +627,7 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
                 if (b < C::NB) gbase[b] = myb[k];
             }
         }
-        eh_bar<9>();
+        eh_bar<BAR.sort, NBAR>();
         if (act) {
             const auto rs = buf_rsrc(cy.R0 + (size_t)nonce * C::ROWS * SW0, (uint32_t)(C::ROWS * SW0 * 4));
             const auto rl = buf_rsrc(cy.LEAF + (size_t)nonce * C::ROWS, (uint32_t)(C::ROWS * 4));
@@ -618,7 +643,7 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
             }
         }
         if (more) start(bn); // the round waves' emit is their longest interval
-        eh_bar<EH_NBAR>();
+        eh_bar<NBAR, NBAR>();
         if (!more) break;
         bk = bn;
         ++it;
@@ -636,8 +661,10 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 //   A. commit: prefetched rows (VGPRs) -> LDS rows (+ parent words when pruning), counting each
 //      row's RB-bit key with a returning LDS atomic (its rank in the key group);
 //      issue the first slice of the next bucket's loads;
-//   D1. key scan: every committed row learns its sorted position;
-//   D2. pair list by per-wave compaction (one barrier), then the pair filter (identical
+//      a slot round also files the row's id in slot `rank` of its key (ranks >= 8: overflow list);
+//   D1. sorted round only. Key scan: every committed row learns its sorted position;
+//   D2. pair list by per-wave compaction (one barrier; a sorted round walks the key group in
+//       sorted order, a slot round reads the key's slots), then the pair filter (identical
 //       subtrees; depth-1 pruning where the round prunes) and the destination histogram;
 //   D3. one atomicAdd per destination bucket claims this bucket's runs there; counting sort of
 //       the pairs by destination;
@@ -650,7 +677,9 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 // LDS (the prune check reads them); every comparison and the emit XOR mask them out (RMI).
 // pdrop holds 2K + 2 counters per nonce. pdrop[STAGE]: pairs lost to a full pair list or to the 14-partner cap of a row in a large key
 // group (duplicate subtrees); pdrop[K + STAGE]: stage-(STAGE-1) rows past the
-// round's capacity (offered to a bucket but never read), counted for every nonce.
+// round's capacity (offered to a bucket but never read), counted for every nonce. Slot rounds
+// also count the rows sent to the overflow list and the most of them in one bucket (EhCfg::PDW).
+// Workgroup barriers per bucket: 10 in a sorted round, 7 in a slot round (eh_bars).
 //
 // CARRY (collision rounds of a configuration with GW > 0): the last GW waves of the workgroup are
 // generation waves. The first C::RNT threads run the round exactly as described above (every
@@ -666,11 +695,16 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     constexpr int WO = (STAGE < C::K) ? C::words(STAGE) : 1;
     constexpr int CAP = C::cap(STAGE);                        // LDS rows / pair-list entries
     constexpr bool FINAL = STAGE == C::K;
-    constexpr int PDW = 2 * C::K + 2;                         // drop counters per nonce
+    constexpr int PDW = C::PDW;                               // counters per nonce
     static_assert(!CARRY || (C::GW > 0 && !FINAL && !STAMP), "only plain collision rounds carry generation");
     constexpr bool PRUNE = round_prunes<C>(STAGE, CARRY);
     static_assert(PRUNE == round_prunes<C>(STAGE), "a carrying round prunes like the plain one");
-    static_assert(round_lds<C>(STAGE, PRUNE, CARRY) <= 160 * 1024 / C::WGCU, "round LDS budget");
+    constexpr bool SLOT = C::ks(STAGE) > 0;                   // slot round: key slots filled at the commit, no key sort
+    constexpr EhBars BAR = eh_bars(SLOT);
+    constexpr int NBAR = BAR.n;                               // workgroup barriers per bucket (eh_carry_gen: the same constant)
+    constexpr int OVL = BCP_EH_OVL;                           // slot round: overflow list entries
+    static_assert((SLOT ? slot_lds<C>(STAGE, PRUNE, CARRY) : round_lds<C>(STAGE, PRUNE, CARRY)) <= 160 * 1024 / C::WGCU,
+                  "round LDS budget");
     constexpr int NT = round_nt<C>(STAGE, CARRY);           // round threads
     static_assert(!CARRY || NT / 64 > 1, "block_exscan runs its two barriers only with more than one wave");
     constexpr int RPL = (CAP + NT - 1) / NT;                // prefetched rows per lane
@@ -694,17 +728,22 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     __shared__ uint32_t psig[PRUNE ? CAP : 1];                // the input rows' parent word (j << 16 | i, + d bits)
     __shared__ uint16_t pdw[PRUNE && !CPI ? CAP : 1];         // two-word parents: the producing bucket
     __shared__ uint32_t npairs;                                // wave-compaction pair list fill
-    __shared__ __attribute__((aligned(16))) uint8_t un[round_un<C>(STAGE, CARRY)];
-    static_assert(FINAL || (sizeof(un) >= (size_t)un_walk_list<C>(CAP) + (size_t)MP * NT * 4),
+    __shared__ uint32_t novf;                                  // slot round: overflow list fill (rows offered to it); else unused
+    __shared__ __attribute__((aligned(16))) uint8_t un[SLOT ? slot_un<C>(STAGE, CARRY) : round_un<C>(STAGE, CARRY)];
+    static_assert(FINAL || SLOT || (sizeof(un) >= (size_t)un_walk_list<C>(CAP) + (size_t)MP * NT * 4),
                   "the union holds sidx, bend and this round's MP * NT pairs");
+    static_assert(!SLOT || (sizeof(un) >= (size_t)un_slot_list<C>() + (size_t)MP * NT * 4 && OVL <= NT && CAP < 0x4000),
+                  "the union holds ktab, bend, ovl and this round's MP * NT pairs; one lane per overflow entry; ranks below the flags");
     __shared__ uint32_t hist_[FINAL ? 1 : C::HW], cur_[FINAL ? 1 : C::HW]; // H16: two 16-bit counters per word
     __shared__ HT base[FINAL ? 1 : C::NB];
     __shared__ uint32_t wsum[NT / 64 + 1];
     __shared__ uint32_t ghist[CARRY ? C::NB : 1], gbase[CARRY ? C::NB : 1]; // the generation waves' tables
     __shared__ uint64_t gr0p[CARRY ? 16 : 1];
-    uint16_t* sidx = reinterpret_cast<uint16_t*>(un);
-    uint32_t* bend = reinterpret_cast<uint32_t*>(un + un_walk_bend<C>(CAP));
-    uint32_t* plist = reinterpret_cast<uint32_t*>(un + un_walk_list<C>(CAP));
+    uint16_t* sidx = reinterpret_cast<uint16_t*>(un); // slot round: ktab[key][rank], the row ids of each key
+    uint16_t* ktab = sidx;
+    uint32_t* bend = reinterpret_cast<uint32_t*>(un + (SLOT ? un_slot_bend<C>() : un_walk_bend<C>(CAP)));
+    uint32_t* ovl = reinterpret_cast<uint32_t*>(un + un_slot_ovl<C>()); // slot round only
+    uint32_t* plist = reinterpret_cast<uint32_t*>(un + (SLOT ? un_slot_list<C>() : un_walk_list<C>(CAP)));
     uint32_t* spair = FOLD ? plist : reinterpret_cast<uint32_t*>(un);
     const int tid = threadIdx.x;
     const int G = gridDim.x;
@@ -831,9 +870,15 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     }
     if constexpr (FOLD) {
         for (int k = tid; k < C::NRESTS; k += NT) bend[k] = 0;
+        if constexpr (SLOT) {
+            if (tid == 0) novf = 0;
+        }
         __syncthreads();
     }
-    const int bk1 = xcd_bucket<C::NB>(blockIdx.x, 1, G, nbk);
+    // slot round: overflow rows of this workgroup's buckets of the current nonce and the most in one
+    // bucket (uniform), written to the nonce's counters when the nonce changes
+    uint32_t ovf_sum = 0, ovf_max = 0;
+    const int bk1 =xcd_bucket<C::NB>(blockIdx.x, 1, G, nbk);
     uint32_t fill_next = bk1 >= 0 ? CTRin[bk1] : 0u;
     // Fill of bucket b (0 for b < 0). As a buffer load it is counted by vmcnt, which barriers do not
     // drain; a plain load of this uniform address would be a scalar load, counted with the LDS
@@ -874,6 +919,26 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     }
                 }
             }
+            // Slot round: every unit's atomic is issued above; the stores that depend on the ranks
+            // follow, so the commit pays one LDS round trip. A row of rank t < 8 files its id in
+            // slot t of its key; a later one goes to the overflow list (bit 14 of krank), or, the
+            // list full, stays off it (bit 15: it keeps its eight table partners).
+            if constexpr (SLOT) {
+#pragma unroll
+                for (int u = 0; u < RPL; ++u) {
+                    const uint32_t r = ot + u * NT;
+                    if (r < n) {
+                        const uint32_t key = krank[u] >> 16, t = krank[u] & 0xffff;
+                        if (t < 8u) {
+                            ktab[key * 8 + t] = (uint16_t)r;
+                        } else {
+                            const uint32_t o = atomicAdd(&novf, 1u);
+                            if (o < (uint32_t)OVL) ovl[o] = (key << 16) | r;
+                            krank[u] |= o < (uint32_t)OVL ? 0x4000u : 0x8000u;
+                        }
+                    }
+                }
+            }
         }
         if constexpr (!FINAL)
             for (int b = tid; b < C::HW; b += NT) hist_[b] = 0;
@@ -890,7 +955,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         const int bn2 = xcd_bucket<C::NB>(blockIdx.x, it + 2, G, nbk);
         issue(0, SLI); // nothing moves when !more (pf_n = 0), but the instruction count stays fixed
         fill_next = fill_of(bn2);
-        eh_bar<1>();
+        eh_bar<1, NBAR>();
         EH_STAMP(2);
 
         // D1. key sort. FOLD: the commit counted the keys; scan to group starts and place each
@@ -899,8 +964,14 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         //     scan, then place (sidx = row ids grouped by key, bend[key] = end of the key's group).
         auto key_of = [&](uint32_t i) -> uint32_t { return rows[i * WI] >> (32 - C::RB); };
         uint32_t kpairs[FOLD ? RPL : 1];
-        if constexpr (FOLD) {
-            EH_BAR_SCAN(2); // barriers 2, 3
+        if constexpr (SLOT) {
+            // no key sort: the commit filed every row under its key. The phase reads as 0 cycles.
+            if constexpr (STAMP) {
+                if (threadIdx.x == 0) stamps[(size_t)bk * 16 + 3] = stamps[(size_t)bk * 16 + 2];
+            }
+            issue(SLI, 2 * SLI);
+        } else if constexpr (FOLD) {
+            EH_BAR_SCAN(2, NBAR); // barriers 2, 3
             block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
             const uint32_t ot = opaque_tid();
 #pragma unroll
@@ -923,9 +994,11 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
             for (uint32_t i = tid; i < n; i += NT) sidx[atomicAdd(&bend[key_of(i)], 1u)] = (uint16_t)i;
         }
-        issue(SLI, 2 * SLI);
-        eh_bar<4>();
-        EH_STAMP(3);
+        if constexpr (!SLOT) {
+            issue(SLI, 2 * SLI);
+            eh_bar<4, NBAR>();
+            EH_STAMP(3);
+        }
 
         if constexpr (FINAL) {
             // D2 (final round). Candidates are pairs equal on ALL remaining bits: each sorted
@@ -954,13 +1027,84 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             //     writes its (j << 16 | i) pairs there: one barrier. The list holds MP*NT pairs
             //     (above the row capacity: capped pair lists lost ~9% of the solutions); identical
             //     subtrees and pairs that share a parent are dropped when the pairs are read back.
+            //     Slot round: a row of rank t in its key group pairs with the rows of smaller rank.
+            //     min(t, 8) of them are the first slots of ktab[key], one 16-byte LDS read, written
+            //     out by a short loop that selects the word in registers (BCP_EH_SLOT_LIST). A row on
+            //     the overflow list (0.6 per bucket) is listed by lane `ordinal`, not its own: all eight table rows, and
+            //     the list entries of its key with a smaller ordinal, at most 6 (the 14-partner cap).
+            //     Every unordered pair of a key group is so listed once, whatever order the atomics
+            //     took. Only when more than OVL rows were offered to the list (never seen) pairs
+            //     among overflow rows are lost; they are counted exactly: every overflow row adds
+            //     its t - 8, every list lane takes off the pairs it lists.
             uint32_t cnt = 0;
+            uint32_t le = 0, lm = 0, ln = 0; // slot round: this lane's list entry, its partners on the list, its pairs
+            if constexpr (SLOT) {
+                const uint32_t nov = __builtin_amdgcn_readfirstlane(novf);
+                const uint32_t NO = min(nov, (uint32_t)OVL);
+                const bool full = nov > (uint32_t)OVL; // uniform
+                ovf_sum += nov;
+                ovf_max = max(ovf_max, nov);
+#pragma unroll
+                for (int u = 0; u < RPL; ++u) {
+                    kpairs[u] = 0;
+                    if (tid + u * NT < n) {
+                        const uint32_t t = krank[u] & 0x3fffu, f = krank[u] & 0xc000u;
+                        kpairs[u] = f == 0x4000u ? 0u : min(t, 8u);
+                        if (full && f) atomicAdd(&pdrop[nonce * PDW + STAGE], t - 8u);
+                    }
+                }
+                if ((uint32_t)tid < NO) {
+                    le = ovl[tid];
+                    uint32_t m = 0;
+                    for (uint32_t q = 0; q < (uint32_t)tid; ++q) m += (ovl[q] >> 16) == (le >> 16) ? 1u : 0u;
+                    lm = min(m, 6u);
+                    if (full) {
+                        if (lm) atomicSub(&pdrop[nonce * PDW + STAGE], lm);
+                    } else if (m > 6u) {
+                        atomicAdd(&pdrop[nonce * PDW + STAGE], m - 6u); // capped pairs (rare) count as pair-list drops
+                    }
+                    ln = 8u + lm;
+                    cnt = ln;
+                }
+            }
 #pragma unroll
             for (int u = 0; u < RPL; ++u) cnt += kpairs[u];
             const uint32_t incl = wave_incl<false>(cnt);
             uint32_t wb = 0;
             if ((tid & 63) == 63) wb = atomicAdd(&npairs, incl);
             uint32_t o = __builtin_amdgcn_readlane(wb, 63) + incl - cnt;
+            if constexpr (SLOT) {
+                // the first c rows of `key`'s slots as partners of row i, at plist[o..]
+                auto table_pairs = [&](uint32_t key, uint32_t c, uint32_t i) {
+                    const u4v w = *reinterpret_cast<const u4v*>(&ktab[key * 8]);
+                    const uint32_t room = o < (uint32_t)(MP * NT) ? (uint32_t)(MP * NT) - o : 0u;
+                    const uint32_t ce = min(c, room);
+                    if constexpr (BCP_EH_SLOT_LIST == 1) { // a short loop with a register select
+                        for (uint32_t q = 0; q < ce; ++q) {
+                            const uint32_t ww = q < 4 ? (q < 2 ? w.x : w.y) : (q < 6 ? w.z : w.w);
+                            plist[o + q] = ((q & 1) ? (ww & 0xffff0000u) : (ww << 16)) | i;
+                        }
+                    } else { // eight predicated stores
+#pragma unroll
+                        for (int q = 0; q < 8; ++q)
+                            if ((uint32_t)q < ce) plist[o + q] = ((q & 1) ? (w[q >> 1] & 0xffff0000u) : (w[q >> 1] << 16)) | i;
+                    }
+                    o += c;
+                };
+#pragma unroll
+                for (int u = 0; u < RPL; ++u)
+                    if (kpairs[u]) table_pairs(krank[u] >> 16, kpairs[u], tid + u * NT);
+                if (ln) {
+                    const uint32_t i = le & 0xffffu;
+                    table_pairs(le >> 16, 8u, i);
+                    for (uint32_t q = 0, k = 0; q < (uint32_t)tid && k < lm; ++q) {
+                        const uint32_t e = ovl[q];
+                        if ((e >> 16) != (le >> 16)) continue;
+                        if (o < (uint32_t)(MP * NT)) plist[o] = (e << 16) | i;
+                        ++o, ++k;
+                    }
+                }
+            } else {
 #pragma unroll
             for (int u = 0; u < RPL; ++u) {
                 if (!kpairs[u]) continue;
@@ -971,7 +1115,8 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     plist[o] = ((uint32_t)sidx[q] << 16) | i;
                 }
             }
-            eh_bar<5>();
+            }
+            eh_bar<BAR.list, NBAR>();
             EH_STAMP(7); // pair list complete (splits D2 into listing and filtering)
             const uint32_t P = npairs;
             const uint32_t Pc = min(P, (uint32_t)(MP * NT));
@@ -995,7 +1140,10 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             }
             // bend's last reads were before the barrier above; the next commit counts here
             for (int k = tid; k < C::NRESTS; k += NT) bend[k] = 0;
-            eh_bar<6>();
+            if constexpr (SLOT) {
+                if (tid == 0) novf = 0; // (read before the barrier above, like bend)
+            }
+            eh_bar<BAR.filter, NBAR>();
             EH_STAMP(4);
             // D3. claim this bucket's runs in the destination areas (device-scope atomics whose
             //     latency hides behind the scan and the scatter), then sort the pairs by
@@ -1011,7 +1159,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             issue(2 * SLI, RPL); // after the claim: waiting for its return then skips these loads
             uint32_t start = 0; // first LDS slot of the thread's first destination
             uint32_t np;
-            EH_BAR_SCAN(7); // barriers 7, 8
+            EH_BAR_SCAN(BAR.scan, NBAR); // sorted round: barriers 7, 8; slot round: 4, 5
             if constexpr (C::H16)
                 np = block_exscan<NT, BPT, uint16_t, uint16_t>(reinterpret_cast<const uint16_t*>(hist_),
                                                                reinterpret_cast<uint16_t*>(cur_), C::NB, wsum, &start);
@@ -1033,7 +1181,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     __builtin_amdgcn_raw_buffer_store_b32(rb, rs_b, b < C::NB ? (uint32_t)b * 4 : OOB, 0, 0);
                 }
             }
-            eh_bar<9>();
+            eh_bar<BAR.sort, NBAR>();
             EH_STAMP(5);
             // D4. emit, one lane per output row in destination order: XOR, shift one digit,
             //     store into the claimed run (rows past the next round's capacity are dropped)
@@ -1073,8 +1221,17 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                 if constexpr (TPO) __builtin_amdgcn_raw_buffer_store_b32(pr, rs_p, t < np ? t * 4 : OOB, 0, 0);
             }
         }
-        eh_bar<EH_NBAR>();
+        eh_bar<NBAR, NBAR>();
         EH_STAMP(6);
+        if constexpr (SLOT) {
+            if (!more || bn / C::NB != nonce) { // uniform: once per nonce and workgroup
+                if (tid == 0 && ovf_sum) {
+                    atomicAdd(&pdrop[nonce * PDW + 2 * C::K + 1 + STAGE], ovf_sum);
+                    atomicMax(&pdrop[nonce * PDW + 3 * C::K + 1 + STAGE], ovf_max);
+                }
+                ovf_sum = ovf_max = 0;
+            }
+        }
         if (!more) break;
         bk = bn;
         ++it;
@@ -1276,8 +1433,8 @@ struct EquihashGpuSolver::Impl {
         d_ctr.alloc((size_t)C::K * batch * C::NB);
         d_leaf.alloc((size_t)batch * C::ROWS);
         d_ncand.alloc(batch);
-        d_pdrop.alloc((size_t)batch * (2 * C::K + 2)); // per nonce, [1..K]: pair-list drops per round, [K+1..2K]: row drops per stage
-        h_pdrop.alloc((size_t)batch * (2 * C::K + 2));
+        d_pdrop.alloc((size_t)batch * C::PDW); // per nonce (EhCfg::PDW): pair-list drops per round, row drops per stage, overflow rows
+        h_pdrop.alloc((size_t)batch * C::PDW);
         d_cand.alloc((size_t)batch * C::MAXCAND);
         d_idx.alloc((size_t)batch * C::MAXCAND * C::L);
         d_valid.alloc((size_t)batch * C::MAXCAND);
@@ -1311,7 +1468,7 @@ struct EquihashGpuSolver::Impl {
         constexpr bool OUT = S < C::K;        // the final round writes candidates, no stage
         constexpr int SO = S < C::K ? S : 0;  // the output stage
         constexpr bool TP = OUT && C::tp(SO); // the output stage's parent tables
-        constexpr size_t PDW = 2 * C::K + 2;
+        constexpr size_t PDW = C::PDW;
         const size_t o = (size_t)noff;
         const uint32_t* rin = d_rst[S - 1].p + o * C::ROWS * C::sw(S - 1);
         uint32_t* rout = OUT ? d_rst[SO].p + o * C::ROWS * C::sw(SO) : nullptr;
@@ -1523,7 +1680,7 @@ struct EquihashGpuSolver::Impl {
         stats.stage_dropped_nonce.assign(ns, 0);
         std::vector<uint64_t> pd(K + 1, 0);
         for (int nn = 0; nn < ns; ++nn) {
-            const uint32_t* q = h_pdrop.p + (size_t)nn * (2 * K + 2);
+            const uint32_t* q = h_pdrop.p + (size_t)nn * C::PDW;
             for (size_t r = 0; r <= K; ++r) {
                 pd[r] += q[r];
                 stats.pair_dropped_all[r] += q[r];
@@ -1532,6 +1689,14 @@ struct EquihashGpuSolver::Impl {
             for (size_t s = 0; s < K; ++s) {
                 stats.stage_dropped_all[s] += q[K + 1 + s];
                 stats.stage_dropped_nonce[nn] += q[K + 1 + s];
+            }
+            if constexpr (C::PDW > 2 * C::K + 2) { // slot rounds: rows past the key slots, and the most in one bucket
+                stats.overflow_rows_all.resize(K + 1, 0);
+                stats.overflow_bucket_max.resize(K + 1, 0);
+                for (size_t r = 1; r <= K; ++r) {
+                    stats.overflow_rows_all[r] += q[2 * K + 1 + r];
+                    stats.overflow_bucket_max[r] = std::max<uint64_t>(stats.overflow_bucket_max[r], q[3 * K + 1 + r]);
+                }
             }
         }
         if (debug) stats.pair_dropped = pd;
@@ -1661,7 +1826,7 @@ struct EquihashGpuSolver::Impl {
 
     // Mean cycles per phase per round (diagnostic stamp builds): [stage][phase delta], deltas
     // 1..6 = commit, next-bucket issue + barrier, key sort, pair enumeration, claim + pair sort, emit;
-    // [0] = whole bucket.
+    // [0] = whole bucket. A slot round has no key sort: it stamps the phase's end with its start, 0 cycles.
     template <class C> std::vector<std::vector<double>> phase_cycles(int nonces) {
         BCP_HIP_CHECK(hipSetDevice(device));
         BCP_HIP_CHECK(hipStreamSynchronize(stream));

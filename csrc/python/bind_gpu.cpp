@@ -144,6 +144,8 @@ void bind_gpu(pyb::module_& m) {
                  d["pair_dropped"] = st.pair_dropped;
                  d["stage_dropped_all"] = st.stage_dropped_all;
                  d["pair_dropped_all"] = st.pair_dropped_all;
+                 d["overflow_rows_all"] = st.overflow_rows_all;
+                 d["overflow_bucket_max"] = st.overflow_bucket_max;
                  d["pair_dropped_nonce"] = st.pair_dropped_nonce;
                  d["stage_dropped_nonce"] = st.stage_dropped_nonce;
                  d["stage_maxfill_all"] = st.stage_maxfill_all;

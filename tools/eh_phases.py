@@ -4,7 +4,9 @@
 python tools/eh_phases.py [--batch 48]   (BCP_NATIVE_PATH selects a build)
 Columns: s_memtime cycles per bucket between the phase stamps of eh_round (see
 EquihashGpuSolver::PhaseCycles): total, commit, issue+barrier, key sort, pairs, claim+pair sort,
-emit, and the pair phase split into listing and filtering.
+emit, and the pair phase split into listing and filtering. A slot round (EhCfg::ks, rounds 3-8
+of a default build) has no key sort: "keysort" reads 0 there, "commit" includes filing the row ids
+under their keys, and "pairs_list" reads the keys' slots instead of walking a sorted order.
 """
 import argparse
 import json
@@ -30,6 +32,7 @@ def main():
         sts.append(st)
     for _ in range(3):
         s.solve(sts)
+    # ("keysort": 0 in a slot round)
     names = ["total", "commit", "issue", "keysort", "pairs", "claim_sort", "emit", "pairs_list", "pairs_filter"]
     for stage, ph in enumerate(s.phase_cycles(a.batch)):
         print(json.dumps({"round": stage + 1, **{n: round(v) for n, v in zip(names, ph)}}), flush=True)
