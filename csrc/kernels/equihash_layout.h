@@ -6,7 +6,7 @@
 // (or the row has no room for the producing bucket), a stage-s slot holds the row followed by its
 // parent word(s), so the emit writes one contiguous slot per output row and the pruning round
 // gets the parents with the rows. The other stages ((200,9): 1-4, 6, 7) keep "table parents"
-// (EhCfg::tp, BCP_EH_TABLE_PARENTS): the slot is the row alone with the producing bucket d in its
+// (EhCfg::tp): the slot is the row alone with the producing bucket d in its
 // padding, so rounds 2..K-1 do not fetch parent words they never use (they share the rows' cache
 // lines); the (j << 16 | i) word of every output row goes, in the emit's destination order, to a
 // per-bucket pair table (consecutive lanes store consecutive words) and the run bases of the
@@ -14,12 +14,16 @@
 // costs ~50 words per slot per nonce (≈17 GB per 32-nonce solver, against 288 GB of HBM); the
 // parents must outlive the rows anyway for the final expansion. Per row per round: one contiguous
 // slot read, one slot write into a claimed run, one pair-table word.
+// The layouts of earlier merges (every slot with its parent words, TABLE_PARENTS=0; every round
+// sorted, KEY_SLOTS=0) are no longer build options: commit 3ff18da is the last tree that builds them.
+// EhRoundGeom (below) gathers the geometry of one round instantiation for the kernel and the host.
 #ifndef BCP_KERNELS_EQUIHASH_LAYOUT_H
 #define BCP_KERNELS_EQUIHASH_LAYOUT_H
 
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #define BCP_EH_HD __host__ __device__
@@ -47,20 +51,19 @@
 #ifndef BCP_EH_GW // (200,9) generation waves of a carrying round workgroup (the round keeps 1024 - 64*GW threads)
 #define BCP_EH_GW 4
 #endif
-#ifndef BCP_EH_TABLE_PARENTS // 1: stages read by a round that does not prune keep their parent words in per-bucket
-#define BCP_EH_TABLE_PARENTS 1 //    tables beside the slot array (EhCfg::tp); 0: every slot carries its parent word(s)
+#ifndef BCP_EH_PF_SLICES // the next bucket's rows are prefetched in this many slices (EhRoundGeom::SLI)
+#define BCP_EH_PF_SLICES 3
 #endif
-
-#ifndef BCP_EH_KEY_SLOTS // slots per key of a "slot round" (EhCfg::ks): the commit files each row's id under its key,
-#define BCP_EH_KEY_SLOTS 8 //   which replaces the key sort. 8 (one 16-byte LDS read per key) or 0: every round sorts
-#endif
-#ifndef BCP_EH_OVL // slot rounds: entries of the overflow list (rows of rank >= BCP_EH_KEY_SLOTS in their key group).
+#ifndef BCP_EH_OVL // slot rounds: entries of the overflow list (rows of rank >= EH_KEY_SLOTS in their key group).
 #define BCP_EH_OVL 128 //   The fullest bucket of the bench's 20 default steps held 16 (profiles/equihash_r10.md)
 #endif
-static_assert(BCP_EH_KEY_SLOTS == 0 || BCP_EH_KEY_SLOTS == 8, "a key's slots are one 16-byte LDS read");
 static_assert(BCP_EH_OVL >= 1 && BCP_EH_OVL <= 128, "the overflow list is walked by the first BCP_EH_OVL lanes");
 
 namespace bcpk {
+
+// Slots per key of a "slot round" (EhCfg::ks): the commit files each row's id under its key, which
+// replaces the key sort. Eight 16-bit row ids are one 16-byte LDS read.
+constexpr int EH_KEY_SLOTS = 8;
 
 // (defined with the round kernels' geometry below; EhCfg's table-parent layout follows from them)
 template <class C> constexpr int round_nt(int stage, bool carry);
@@ -137,8 +140,8 @@ struct EhCfg {
     // Only eh_expand reads P and B: the rounds 2..K-1 that read such a stage fetch rows alone.
     static constexpr int pad(int stage) { return 32 * words(stage) - bits(stage); }
     static constexpr bool tp(int stage) {
-        return BCP_EH_TABLE_PARENTS && stage >= 1 && stage <= K - 2 && !round_prunes<EhCfg>(stage + 1) &&
-               !round_prunes<EhCfg>(stage + 1, true) && pad(stage) >= BB;
+        return stage >= 1 && stage <= K - 2 && !round_prunes<EhCfg>(stage + 1) && !round_prunes<EhCfg>(stage + 1, true) &&
+               pad(stage) >= BB;
     }
     // pair-table words per producing bucket: every ordinal the emit of either variant can hold
     static constexpr int ptab(int stage) {
@@ -162,14 +165,12 @@ struct EhCfg {
     // rows in LDS, plain and carrying: (200,9) rounds 3..8 (1 and 2 would take ~174 KB), every collision
     // round of (96,5). The final round keeps the sort.
     static constexpr int ks(int stage) {
-        return BCP_EH_KEY_SLOTS && stage >= 1 && stage < K && NRESTS >= 256 && slot_round_fits<EhCfg>(stage)
-                   ? BCP_EH_KEY_SLOTS
-                   : 0;
+        return stage >= 1 && stage < K && NRESTS >= 256 && slot_round_fits<EhCfg>(stage) ? EH_KEY_SLOTS : 0;
     }
     // Counters per nonce (pdrop): [1..K] pairs dropped per round, [K+1..2K] rows dropped per
-    // stage; with slot rounds also [2K+2..3K+1] overflow rows per round (2K+1+round) and
-    // [3K+2..4K+1] the most overflow rows one bucket of the round had (3K+1+round).
-    static constexpr int PDW = 2 * K + 2 + (BCP_EH_KEY_SLOTS ? 2 * K : 0);
+    // stage, [2K+2..3K+1] overflow rows per slot round (2K+1+round) and [3K+2..4K+1] the most
+    // overflow rows one bucket of the round had (3K+1+round).
+    static constexpr int PDW = 4 * K + 2;
     // 16-bit LDS histograms (two counters per word) where 32-bit ones would not fit two per CU
     static constexpr bool H16 = NB > 512;
     static constexpr int HW = H16 ? NB / 2 : NB;      // words per histogram
@@ -290,6 +291,63 @@ template <class C> constexpr bool slot_round_fits(int stage) {
     return slot_lds<C>(stage, round_prunes<C>(stage, false), false) <= C::LDS_BUDGET &&
            (C::GW == 0 || slot_lds<C>(stage, round_prunes<C>(stage, true), true) <= C::LDS_BUDGET);
 }
+
+// The geometry of one instantiation of the round kernel, eh_round<C, STAGE, *, CARRY>: what the
+// kernel, its phase functions, the generation waves it carries (eh_carry_gen) and the host launch
+// read. STAGE < K: the collision round producing stage STAGE; STAGE == K: the final round.
+template <class C, int STAGE_, bool CARRY_> struct EhRoundGeom {
+    using Cfg = C;
+    static constexpr int STAGE = STAGE_;
+    static constexpr bool CARRY = CARRY_;
+    static constexpr bool FINAL = STAGE == C::K;
+    static constexpr int WI = C::words(STAGE - 1);             // words per input row (LDS words per row)
+    static constexpr int WO = FINAL ? 1 : C::words(STAGE);     // words per output row
+    static constexpr int CAP = C::cap(STAGE);                  // LDS rows
+    static constexpr bool PRUNE = round_prunes<C>(STAGE, CARRY);
+    static constexpr bool SLOT = C::ks(STAGE) > 0;             // slot round: key slots filled at the commit, no key sort
+    static constexpr EhBars BAR = eh_bars(SLOT);
+    static constexpr int NBAR = BAR.n;                         // workgroup barriers per bucket, round and generation waves alike
+    static constexpr int NT = round_nt<C>(STAGE, CARRY);       // round threads
+    static constexpr int RPL = (CAP + NT - 1) / NT;            // prefetched rows per lane
+    static constexpr int MP = round_mp<C>(STAGE, CARRY);       // pairs per lane (registers)
+    static constexpr int NPAIR = MP * NT;                      // pair-list entries
+    static constexpr int SWI = C::sw(STAGE - 1);               // words per input slot
+    static constexpr int SWO = FINAL ? 1 : C::sw(STAGE);       // words per output slot
+    static constexpr bool TPO = !FINAL && C::tp(STAGE);        // output stage keeps its parents in tables (Pout, Bout)
+    static constexpr int PTW = TPO ? C::ptab(STAGE) : 1;       // pair-table words per producing bucket
+    static constexpr bool CPI = C::cp(STAGE - 1);              // input slots carry one compact parent word
+    static constexpr uint32_t RMI = C::rmask(STAGE - 1);       // parent bits in the input rows' padding
+    static constexpr uint32_t RMO = C::rmask(STAGE);           // ... and in the output rows'
+    static constexpr uint32_t OCAP = C::cap(FINAL ? C::K : STAGE + 1); // capacity of the round that reads the output
+    static constexpr int SLI = (RPL + BCP_EH_PF_SLICES - 1) / BCP_EH_PF_SLICES; // prefetch slice (rows per phase)
+    static constexpr int BPT = (C::NB + NT - 1) / NT;          // destination buckets per thread (claims)
+    static constexpr int LWI = PRUNE ? (CPI ? WI + 1 : WI + 2) : WI; // words loaded per slot: a round that does not prune loads the row alone
+    static constexpr int OVL = BCP_EH_OVL;                     // slot round: overflow list entries
+    using HT = std::conditional_t<C::H16, uint16_t, uint32_t>; // histogram / run-base entry
+    // the LDS arrays beside the union, as eh_round declares them and its phases take them
+    using Rows = uint32_t[(CAP * WI + 3) / 4 * 4];
+    using Psig = uint32_t[PRUNE ? CAP : 1];                    // the input rows' parent word (pruning round)
+    using Pdw = uint16_t[PRUNE && !CPI ? CAP : 1];             // two-word parents: the producing bucket
+    using Hist = uint32_t[FINAL ? 1 : C::HW];                  // H16: two 16-bit counters per word
+    using Base = HT[FINAL ? 1 : C::NB];
+    using Wsum = uint32_t[NT / 64 + 1];
+    // the phase-D union: its bytes and the offsets of bend, ovl (slot round only) and plist inside it
+    static constexpr int UN_BYTES = SLOT ? slot_un<C>(STAGE, CARRY) : round_un<C>(STAGE, CARRY);
+    static constexpr int UN_BEND = SLOT ? un_slot_bend<C>() : un_walk_bend<C>(CAP);
+    static constexpr int UN_OVL = un_slot_ovl<C>();
+    static constexpr int UN_PLIST = SLOT ? un_slot_list<C>() : un_walk_list<C>(CAP);
+    static constexpr int LDS_BYTES = SLOT ? slot_lds<C>(STAGE, PRUNE, CARRY) : round_lds<C>(STAGE, PRUNE, CARRY);
+
+    static_assert(!CARRY || (C::GW > 0 && !FINAL), "only collision rounds carry generation");
+    static_assert(PRUNE == round_prunes<C>(STAGE), "a carrying round prunes like the plain one");
+    static_assert(LDS_BYTES <= C::LDS_BUDGET, "round LDS budget");
+    static_assert(!CARRY || NT / 64 > 1, "block_exscan runs its two barriers only with more than one wave");
+    static_assert(!TPO || PTW >= NPAIR, "the pair table holds every ordinal this round's emit can have (the spair bound)");
+    static_assert(!(PRUNE && C::tp(STAGE - 1)), "a pruning round reads its parents from the slots");
+    static_assert(FINAL || SLOT || UN_BYTES >= UN_PLIST + NPAIR * 4, "the union holds sidx, bend and this round's MP * NT pairs");
+    static_assert(!SLOT || (UN_BYTES >= UN_PLIST + NPAIR * 4 && OVL <= NT && CAP < 0x4000),
+                  "the union holds ktab, bend, ovl and this round's MP * NT pairs; one lane per overflow entry; ranks below the flags");
+};
 
 // Generation carried by the collision rounds of the previous nonce group. The (K-1)*NB bucket
 // iterations that rounds 1..K-1 spend on a nonce hash that nonce's partner in the next group:

@@ -60,18 +60,13 @@
 #include <stdexcept>
 #include <utility>
 
-// Build options (each either the measured default or covered by the GPU tests; the variants that
-// were measured and rejected in rounds 3-5 are at git tag solver-r5-knobs, profiles/equihash_r4.md
-// and profiles/equihash_r5.md; the options that shape the layout are in equihash_layout.h):
-#ifndef BCP_EH_XCD_MAP // 1: every kernel of a nonce runs on one XCD (nonce % 8), so the run writes
-#define BCP_EH_XCD_MAP 1  //    of a nonce meet in one L2 (batches that are a multiple of 8 nonces)
-#endif
-#ifndef BCP_EH_PF_SLICES // the next bucket's rows are prefetched in this many slices
-#define BCP_EH_PF_SLICES 3
-#endif
-#ifndef BCP_EH_SLOT_LIST // slot rounds, how a row writes out the pairs with its key's slots: 1 = a short loop with a
-#define BCP_EH_SLOT_LIST 1 //   register select; 0 = eight predicated stores, fully unrolled: 0.7% fewer Sol/s and 300-700
-#endif                     //   more cycles per bucket (profiles/equihash_r10.md)
+// Build options: numeric tuning values only (each either the measured default or covered by the GPU
+// tests; the options that shape the layout are in equihash_layout.h). Variants whose A/B is over are
+// not kept as switches: those measured and rejected in rounds 3-5 are at git tag solver-r5-knobs
+// (profiles/equihash_r4.md, profiles/equihash_r5.md); the unmapped work order (XCD_MAP=0, 16-23%
+// slower in rounds 1-4), the unrolled slot listing (SLOT_LIST=0, profiles/equihash_r10.md), the
+// all-sorted rounds (KEY_SLOTS=0) and the slots with parent words everywhere (TABLE_PARENTS=0,
+// profiles/equihash_r8.md) were last buildable at commit 3ff18da.
 #ifndef BCP_EH_SLOT_RB // generation waves of a carrying slot round: the BLAKE2b round at which the slice of the
 #define BCP_EH_SLOT_RB 5 //   commit interval stops, and (BCP_EH_SLOT_RD) the slice of the pair-listing interval
 #endif
@@ -252,7 +247,7 @@ constexpr int NXCD = 8;
 // it-th bucket of workgroup b among nbk = NB * nonces buckets (grid G); -1 when done.
 template <int NB> __device__ __forceinline__ int xcd_bucket(int b, int it, int G, int nbk) {
     const int nonces = nbk / NB;
-    if (!BCP_EH_XCD_MAP || G % NXCD || nonces % NXCD) {
+    if (G % NXCD || nonces % NXCD) { // (grids and batches that are no multiple of 8: plain striding)
         const int bk = b + it * G;
         return bk < nbk ? bk : -1;
     }
@@ -262,6 +257,22 @@ template <int NB> __device__ __forceinline__ int xcd_bucket(int b, int it, int G
 }
 
 // ------------------------------------------------------------------ stage 0
+// The tail of register generation (eh_gen_reg, eh_carry_gen): the row whose rank word is rk
+// ((rank in this workgroup's run << 16) | bucket) goes to run position base_d + rank of its bucket
+// in the stage-0 array (rs) and its leaf index li to LEAF (rl). A row that is not `live` or lies
+// past the first round's capacity is stored at the out-of-range offset: the store stream is fixed.
+template <class C>
+__device__ __forceinline__ void eh_gen_store(__amdgpu_buffer_rsrc_t rs, __amdgpu_buffer_rsrc_t rl, uint32_t rk, uint32_t base_d,
+                                             bool live, uint32_t li, const uint32_t* row) {
+    constexpr int SW0 = C::sw(0);
+    const uint32_t d = rk & 0xffff;
+    const uint32_t pos = base_d + (rk >> 16);
+    const uint32_t slot = d * C::AREA + pos;
+    const bool ok = live && pos < (uint32_t)C::cap(1);
+    row_store<C::words(0)>(rs, ok ? slot * (SW0 * 4) : OOB, row);
+    __builtin_amdgcn_raw_buffer_store_b32(li, rl, ok ? slot * 4 : OOB, 0, 0);
+}
+
 // Generation workgroup gw of a nonce hashes rows [gw*RPW, (gw+1)*RPW), counting-sorts them by
 // bucket in LDS, claims one run per destination bucket (device-scope atomicAdd on the stage-0
 // fill counters CTR0[nonce][NB]) and writes every row into its run; the leaf index of each
@@ -352,7 +363,6 @@ __global__ __launch_bounds__(NTG) __attribute__((amdgpu_waves_per_eu(1))) void e
     static_assert(G::OK, "register generation geometry");
     constexpr int W0 = C::words(0);
     constexpr int SW = (C::N + 31) / 32 + 1;
-    constexpr uint32_t OCAP = C::cap(1);
     __shared__ uint32_t hist[C::NB], base[C::NB];
     __shared__ uint64_t r0p[HDR ? 16 : 1]; // the nonce's g-independent round-0 prefix
     const int tid = threadIdx.x;
@@ -361,7 +371,7 @@ __global__ __launch_bounds__(NTG) __attribute__((amdgpu_waves_per_eu(1))) void e
     for (int b = blockIdx.x; b < items; b += gridDim.x) {
     int gw = b % G::GWG;
     int nonce = b / G::GWG;
-    if (BCP_EH_XCD_MAP && (items / G::GWG) % NXCD == 0 && gridDim.x % NXCD == 0) { // nonce n's workgroups on XCD n % 8
+    if ((items / G::GWG) % NXCD == 0 && gridDim.x % NXCD == 0) { // nonce n's workgroups on XCD n % 8
         const int x = b % NXCD, j = b / NXCD;
         gw = j % G::GWG;
         nonce = x + NXCD * (j / G::GWG);
@@ -427,13 +437,9 @@ __global__ __launch_bounds__(NTG) __attribute__((amdgpu_waves_per_eu(1))) void e
 #pragma unroll
     for (int q = 0; q < G::RPT; ++q) {
         const uint32_t d = rk[q] & 0xffff;
-        const uint32_t pos = base[d] + (rk[q] >> 16);
-        const uint32_t slot = d * C::AREA + pos;
-        const bool ok = pos < OCAP;
         const uint32_t g = g0 + (q / C::IPH) * NTG + tid;
         const uint32_t li = g * C::IPH + (q % C::IPH); // leaf index
-        row_store<W0>(rs, ok ? slot * (SW0 * 4) : OOB, rw[q]);
-        __builtin_amdgcn_raw_buffer_store_b32(li, rl, ok ? slot * 4 : OOB, 0, 0);
+        eh_gen_store<C>(rs, rl, rk[q], base[d], true, li, rw[q]);
     }
     }
 }
@@ -499,9 +505,8 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
     constexpr int SW = (C::N + 31) / 32 + 1;
     constexpr int SW0 = C::sw(0);
     constexpr int GT = GC::GT, HB = GC::HB;
-    constexpr uint32_t OCAP = C::cap(1);
     const int gtid = (int)threadIdx.x - C::RNT;
-    const int G = gridDim.x;
+    const int grid = gridDim.x;
     // chunk of bucket b, or -1 when there is nothing to generate (uniform)
     auto chunk_of = [&](int b) -> int {
         const int nonce = b / C::NB, c = (STAGE - 1) * C::NB + b % C::NB;
@@ -518,9 +523,10 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
     // BLAKE2b round at which each slice stops (round 0 belongs to begin())
     // in the round's emit / commit / key placement / pair listing interval; the pair filter
     // interval takes the rest (the schedules measured are in profiles/equihash_r7.md)
-    constexpr bool SLOT = C::ks(STAGE) > 0;
-    constexpr EhBars BAR = eh_bars(SLOT);
-    constexpr int NBAR = BAR.n;
+    using G = EhRoundGeom<C, STAGE, true>; // the round these waves are part of
+    constexpr bool SLOT = G::SLOT;
+    constexpr EhBars BAR = G::BAR;
+    constexpr int NBAR = G::NBAR;
     constexpr int RA = 3, RB = SLOT ? BCP_EH_SLOT_RB : 5, RC = SLOT ? RB : 6, RD = SLOT ? BCP_EH_SLOT_RD : 10;
     static_assert(RA <= RB && RB <= RC && RC <= RD && RD <= 12, "BLAKE2b slices in order");
     EhHdrHash hs[HB];
@@ -539,7 +545,7 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
         }
     };
     int it = 0;
-    int bk = xcd_bucket<C::NB>(blockIdx.x, 0, G, nbk); // >= 0: the caller returned otherwise
+    int bk = xcd_bucket<C::NB>(blockIdx.x, 0, grid, nbk); // >= 0: the caller returned otherwise
     for (int i = gtid; i < C::NB; i += GT) ghist[i] = 0;
     prefix(bk);
     __syncthreads(); // the prologue barrier
@@ -549,7 +555,7 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
         const int chunk = chunk_of(bk);
         const bool act = chunk >= 0; // uniform
         const EhBaseState& bs = cy.states[act ? nonce : 0];
-        const int bn = xcd_bucket<C::NB>(blockIdx.x, it + 1, G, nbk);
+        const int bn = xcd_bucket<C::NB>(blockIdx.x, it + 1, grid, nbk);
         const bool more = bn >= 0; // uniform, the round waves' loop-exit test
         const uint32_t g0 = (uint32_t)chunk * GC::CH + (uint32_t)gtid;
         uint32_t rw[GC::RPT][W0];
@@ -634,12 +640,8 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 #pragma unroll
             for (int q = 0; q < GC::RPT; ++q) {
                 const uint32_t d = rk[q] & 0xffff;
-                const uint32_t pos = gbase[d < (uint32_t)C::NB ? d : 0] + (rk[q] >> 16);
-                const uint32_t slot = d * C::AREA + pos;
-                const bool ok = rk[q] != NIL && pos < OCAP;
                 const uint32_t li = (g0 + (q / C::IPH) * GT) * C::IPH + (q % C::IPH); // leaf index
-                row_store<W0>(rs, ok ? slot * (SW0 * 4) : OOB, rw[q]);
-                __builtin_amdgcn_raw_buffer_store_b32(li, rl, ok ? slot * 4 : OOB, 0, 0);
+                eh_gen_store<C>(rs, rl, rk[q], gbase[d < (uint32_t)C::NB ? d : 0], rk[q] != NIL, li, rw[q]);
             }
         }
         if (more) start(bn); // the round waves' emit is their longest interval
@@ -685,70 +687,210 @@ __device__ __forceinline__ void eh_carry_gen(const EhCarry& cy, int nbk, uint32_
 // generation waves. The first C::RNT threads run the round exactly as described above (every
 // per-workgroup size below is taken from that thread count); the generation waves run
 // eh_carry_gen between the same workgroup barriers.
+//
+// The phases that come out of the kernel without costing registers are the function templates
+// below: the prefetch issue (identical code), the key sort, the final round's candidate search and
+// the sorted round's listing (sorted and final rounds change slightly, within the register bounds;
+// the slot rounds stay byte-identical). G is the round's EhRoundGeom (equihash_layout.h). The
+// commit, the slot listing, the pair filter, the run claim, the pair sort and the emit stay inline
+// in eh_round: each of them as a function cost SGPR spills or more than two VGPRs in some round
+// (profiles/equihash_r11.md has the per-phase table), and so does sharing eh_shares_parent or
+// opaque_tid with the lambdas of the same name in eh_round.
+
+// (keep in step with the lambda of the same name in eh_round, which the inline phases use)
+// A thread id the compiler cannot see through: keeps the per-lane index math of the
+// prefetch/commit loops from being hoisted out of the persistent loop (live invariants
+// would otherwise push the prefetched rows out to scratch).
+__device__ __forceinline__ uint32_t opaque_tid() {
+    const int tid = threadIdx.x;
+    uint32_t t;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(tid));
+    return t;
+}
+
+// rows i and j share a parent (depth-1 duplicate): equal producing bucket and a common LDS row
+// (keep in step with the shares_parent lambda in eh_round, which the inline pair filter uses)
+template <class G>
+__device__ __forceinline__ bool eh_shares_parent(const typename G::Rows& rows, const typename G::Psig& psig, const typename G::Pdw& pdw, uint32_t i,
+                                                 uint32_t j) {
+    using C = typename G::Cfg;
+    constexpr int WI = G::WI;
+    const uint32_t a = psig[i], b = psig[j];
+    const uint32_t ai = a & C::IMASK, bi = b & C::IMASK;
+    const bool hit = (ai & 0xffff) == (bi & 0xffff) || (ai & 0xffff) == (bi >> 16) ||
+                     (ai >> 16) == (bi & 0xffff) || (ai >> 16) == (bi >> 16);
+    if (!hit) return false;
+    if constexpr (G::CPI)
+        return ((a ^ b) & ~C::IMASK) == 0 && ((rows[i * WI + WI - 1] ^ rows[j * WI + WI - 1]) & G::RMI) == 0;
+    else
+        return pdw[i] == pdw[j];
+}
+
+// Prefetch issue: the loads of rows [u0, u1) per lane of bucket pf_bk (pf_n rows) into nr. Reads
+// Rin; no barrier on either side (the loads stay in flight across barriers until the commit).
+// Every vector-memory instruction of the loop body is issued unconditionally (lanes with nothing
+// to move use an out-of-range buffer offset, which the descriptor's range check drops), so the
+// compiler can count the outstanding operations and wait for the prefetched words with a precise
+// vmcnt(N) instead of vmcnt(0): a vmcnt(0) at the commit would wait for the acks of the previous
+// bucket's emit stores as well.
+template <class G>
+__device__ __forceinline__ void eh_prefetch(const uint32_t* Rin, int pf_bk, uint32_t pf_n, int u0, int u1,
+                                            uint32_t (&nr)[G::RPL][G::LWI]) {
+    using C = typename G::Cfg;
+    const int nonce = pf_bk / C::NB, d = pf_bk % C::NB;
+    const auto rs = buf_rsrc(Rin + ((size_t)nonce * C::ROWS + (size_t)d * C::AREA) * G::SWI, G::CAP * G::SWI * 4);
+    const uint32_t ot = opaque_tid();
+#pragma unroll
+    for (int u = 0; u < G::RPL; ++u) {
+        if (u < u0 || u >= u1) continue;
+        const uint32_t r = ot + u * G::NT;
+        row_load<G::LWI>(rs, r < pf_n ? r * (G::SWI * 4) : OOB, nr[u]);
+    }
+}
+
+// D1. key sort of a sorted round, between barriers 1 and 4 (the scan runs barriers 2 and 3).
+// Collision round: the commit counted the keys; scan bend to group starts and place each row by
+// its rank: sidx = row ids grouped by key, krank = the row's sorted position, kpairs = the number of
+// later positions in its key group (its pairs, capped at 14; the excess counts as pair drops).
+// Final round: count, scan, then place (sidx as above, bend[key] = end of the key's group).
+template <class G>
+__device__ __forceinline__ void eh_key_sort(const typename G::Rows& rows, uint32_t* bend, uint16_t* sidx, typename G::Wsum& wsum,
+                                            uint32_t* pdrop, int nonce, uint32_t n, uint32_t (&krank)[G::FINAL ? 1 : G::RPL],
+                                            uint32_t (&kpairs)[G::FINAL ? 1 : G::RPL]) {
+    using C = typename G::Cfg;
+    constexpr int NT = G::NT;
+    const int tid = threadIdx.x;
+    if constexpr (!G::FINAL) {
+        EH_BAR_SCAN(2, G::NBAR); // barriers 2, 3
+        block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
+        const uint32_t ot = opaque_tid();
+#pragma unroll
+        for (int u = 0; u < G::RPL; ++u) {
+            const uint32_t r = ot + u * NT;
+            kpairs[u] = 0;
+            if (r < n) {
+                const uint32_t key = krank[u] >> 16;
+                const uint32_t pos = bend[key] + (krank[u] & 0xffff);
+                const uint32_t e = key + 1 < (uint32_t)C::NRESTS ? bend[key + 1] : n;
+                sidx[pos] = (uint16_t)r;
+                krank[u] = pos;
+                kpairs[u] = min(e - pos - 1, 14u);
+                if (e - pos - 1 > 14u) atomicAdd(&pdrop[nonce * C::PDW + G::STAGE], e - pos - 1 - 14u); // capped pairs (rare) count as pair-list drops
+            }
+        }
+    } else {
+        auto key_of = [&](uint32_t i) -> uint32_t { return rows[i * G::WI] >> (32 - C::RB); };
+        for (uint32_t i = tid; i < n; i += NT) atomicAdd(&bend[key_of(i)], 1u);
+        __syncthreads();
+        block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
+        for (uint32_t i = tid; i < n; i += NT) sidx[atomicAdd(&bend[key_of(i)], 1u)] = (uint16_t)i;
+    }
+}
+
+// D2, final round: the candidate search, after barrier 4, before the last barrier. Reads rows,
+// sidx, bend (psig, pdw); writes ncand and cand. Candidates are pairs equal on ALL remaining bits:
+// each sorted position scans the rest of its key group (a few rows). No pair list, so a bucket's
+// pair count is not capped (a capped list here silently lost solutions).
+template <class G>
+__device__ __forceinline__ void eh_final_candidates(const typename G::Rows& rows, const typename G::Psig& psig, const typename G::Pdw& pdw,
+                                                    const uint16_t* sidx, const uint32_t* bend, uint32_t* ncand, uint64_t* cand,
+                                                    int nonce, int d, uint32_t n) {
+    using C = typename G::Cfg;
+    static_assert(G::WI == 1, "final-round rows are one word");
+    const int tid = threadIdx.x;
+    for (uint32_t p = tid; p < n; p += G::NT) {
+        const uint32_t i = sidx[p], ri = rows[i], e = bend[ri >> (32 - C::RB)];
+        for (uint32_t q = p + 1; q < e; ++q) {
+            const uint32_t j = sidx[q];
+            if ((rows[j] ^ ri) & ~G::RMI) continue;
+            if constexpr (G::PRUNE) {
+                if (eh_shares_parent<G>(rows, psig, pdw, i, j)) continue;
+            }
+            const uint32_t c = atomicAdd(&ncand[nonce], 1u);
+            if (c < (uint32_t)C::MAXCAND) cand[(size_t)nonce * C::MAXCAND + c] = pack_tri(d, i, j);
+        }
+    }
+}
+
+// D2. pair list by per-wave compaction, before barrier BAR.list (after barrier 4 in a sorted round,
+// 1 in a slot round). Each lane has counted the pairs of the rows it committed (kpairs, registers;
+// cnt: the lane's other pairs), a DPP wave scan gives the lane's offset inside its wave, ONE LDS
+// atomic per wave claims the wave's block of the list (npairs): returns the lane's first entry.
+// The list holds MP*NT pairs (above the row capacity: capped pair lists lost ~9% of the
+// solutions); identical subtrees and pairs that share a parent are dropped when the pairs are read
+// back (eh_filter).
+template <class G>
+__device__ __forceinline__ uint32_t eh_list_claim(uint32_t cnt, const uint32_t (&kpairs)[G::RPL], uint32_t& npairs) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < G::RPL; ++u) cnt += kpairs[u];
+    const uint32_t incl = wave_incl<false>(cnt);
+    uint32_t wb = 0;
+    if ((tid & 63) == 63) wb = atomicAdd(&npairs, incl);
+    return __builtin_amdgcn_readlane(wb, 63) + incl - cnt;
+}
+
+// D2, sorted round. Reads sidx, krank and kpairs; writes plist and npairs. Sorted position p pairs
+// with every later position of its key group: c_p = bend[key] - p - 1 pairs (capped at 14; a group
+// of 16+ rows is ~1e-8 likely), the lane writes its (j << 16 | i) pairs into its part of the list.
+template <class G>
+__device__ __forceinline__ void eh_list_sorted(const uint16_t* sidx, uint32_t* plist, uint32_t& npairs,
+                                               const uint32_t (&krank)[G::RPL], const uint32_t (&kpairs)[G::RPL]) {
+    const int tid = threadIdx.x;
+    uint32_t o = eh_list_claim<G>(0, kpairs, npairs);
+#pragma unroll
+    for (int u = 0; u < G::RPL; ++u) {
+        if (!kpairs[u]) continue;
+        const uint32_t p = krank[u];
+        const uint32_t i = tid + u * G::NT;
+        for (uint32_t q = p + 1; q <= p + kpairs[u]; ++q, ++o) {
+            if (o >= (uint32_t)G::NPAIR) continue;
+            plist[o] = ((uint32_t)sidx[q] << 16) | i;
+        }
+    }
+}
+
+// The kernel. EhRoundGeom gives the geometry; the local names below are the ones the inline phases use.
 template <class C, int STAGE, bool STAMP, bool CARRY = false>
 __global__ __launch_bounds__(C::NT) __attribute__((amdgpu_waves_per_eu(C::WGCU * C::NT / 256)))
 void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTRin, uint32_t* __restrict__ Rout,
               uint32_t* __restrict__ CTRout, uint32_t* __restrict__ Pout, uint32_t* __restrict__ Bout,
               uint32_t* __restrict__ ncand, uint64_t* __restrict__ cand, uint64_t* __restrict__ stamps,
               uint32_t* __restrict__ pdrop, int nbk, EhCarry carry) {
-    constexpr int WI = C::words(STAGE - 1);
-    constexpr int WO = (STAGE < C::K) ? C::words(STAGE) : 1;
-    constexpr int CAP = C::cap(STAGE);                        // LDS rows / pair-list entries
-    constexpr bool FINAL = STAGE == C::K;
-    constexpr int PDW = C::PDW;                               // counters per nonce
-    static_assert(!CARRY || (C::GW > 0 && !FINAL && !STAMP), "only plain collision rounds carry generation");
-    constexpr bool PRUNE = round_prunes<C>(STAGE, CARRY);
-    static_assert(PRUNE == round_prunes<C>(STAGE), "a carrying round prunes like the plain one");
-    constexpr bool SLOT = C::ks(STAGE) > 0;                   // slot round: key slots filled at the commit, no key sort
-    constexpr EhBars BAR = eh_bars(SLOT);
-    constexpr int NBAR = BAR.n;                               // workgroup barriers per bucket (eh_carry_gen: the same constant)
-    constexpr int OVL = BCP_EH_OVL;                           // slot round: overflow list entries
-    static_assert((SLOT ? slot_lds<C>(STAGE, PRUNE, CARRY) : round_lds<C>(STAGE, PRUNE, CARRY)) <= 160 * 1024 / C::WGCU,
-                  "round LDS budget");
-    constexpr int NT = round_nt<C>(STAGE, CARRY);           // round threads
-    static_assert(!CARRY || NT / 64 > 1, "block_exscan runs its two barriers only with more than one wave");
-    constexpr int RPL = (CAP + NT - 1) / NT;                // prefetched rows per lane
-    constexpr int MP = round_mp<C>(STAGE, CARRY);           // pairs per lane (registers)
-    constexpr int SWI = C::sw(STAGE - 1);                  // words per input slot
-    constexpr int SWO = STAGE < C::K ? C::sw(STAGE) : 1;   // words per output slot
-    constexpr bool TPO = !FINAL && C::tp(STAGE);           // output stage keeps its parents in tables (Pout, Bout)
-    constexpr int PTW = TPO ? C::ptab(STAGE) : 1;          // pair-table words per producing bucket
-    static_assert(!TPO || PTW >= MP * NT, "the pair table holds every ordinal this round's emit can have (the spair bound)");
-    static_assert(!(PRUNE && C::tp(STAGE - 1)), "a pruning round reads its parents from the slots");
-    constexpr bool CPI = C::cp(STAGE - 1);                 // input slots carry one compact parent word
-    constexpr uint32_t RMI = C::rmask(STAGE - 1);          // parent bits in the input rows' padding
-    constexpr int SLI = (RPL + BCP_EH_PF_SLICES - 1) / BCP_EH_PF_SLICES; // prefetch slice (rows per phase)
-    constexpr int BPT = (C::NB + NT - 1) / NT;             // destination buckets per thread (claims)
+    using G = EhRoundGeom<C, STAGE, CARRY>;
+    static_assert(!CARRY || !STAMP, "only plain collision rounds carry generation");
+    constexpr bool FINAL = G::FINAL, PRUNE = G::PRUNE, SLOT = G::SLOT, TPO = G::TPO, CPI = G::CPI;
+    constexpr int WI = G::WI, WO = G::WO, CAP = G::CAP, NT = G::NT, RPL = G::RPL, MP = G::MP, SWI = G::SWI, SWO = G::SWO;
+    constexpr int PTW = G::PTW, SLI = G::SLI, BPT = G::BPT, LWI = G::LWI, OVL = G::OVL, PDW = C::PDW;
+    constexpr uint32_t RMI = G::RMI, RMO = G::RMO, OCAP = G::OCAP;
+    constexpr EhBars BAR = G::BAR;
+    constexpr int NBAR = G::NBAR; // workgroup barriers per bucket (eh_carry_gen: the same constant)
     // key counting folded into the commit (collision rounds): bend holds counts after the commit
     // and group starts after the scan; spair then aliases the pair list, so bend survives the
     // emit and is cleared for the next bucket in D3
     constexpr bool FOLD = !FINAL;
-    using HT = std::conditional_t<C::H16, uint16_t, uint32_t>;
-    __shared__ __attribute__((aligned(16))) uint32_t rows[(CAP * WI + 3) / 4 * 4];
-    __shared__ uint32_t psig[PRUNE ? CAP : 1];                // the input rows' parent word (j << 16 | i, + d bits)
-    __shared__ uint16_t pdw[PRUNE && !CPI ? CAP : 1];         // two-word parents: the producing bucket
+    using HT = typename G::HT;
+    __shared__ __attribute__((aligned(16))) typename G::Rows rows;
+    __shared__ typename G::Psig psig;                          // the input rows' parent word (j << 16 | i, + d bits)
+    __shared__ typename G::Pdw pdw;                            // two-word parents: the producing bucket
     __shared__ uint32_t npairs;                                // wave-compaction pair list fill
     __shared__ uint32_t novf;                                  // slot round: overflow list fill (rows offered to it); else unused
-    __shared__ __attribute__((aligned(16))) uint8_t un[SLOT ? slot_un<C>(STAGE, CARRY) : round_un<C>(STAGE, CARRY)];
-    static_assert(FINAL || SLOT || (sizeof(un) >= (size_t)un_walk_list<C>(CAP) + (size_t)MP * NT * 4),
-                  "the union holds sidx, bend and this round's MP * NT pairs");
-    static_assert(!SLOT || (sizeof(un) >= (size_t)un_slot_list<C>() + (size_t)MP * NT * 4 && OVL <= NT && CAP < 0x4000),
-                  "the union holds ktab, bend, ovl and this round's MP * NT pairs; one lane per overflow entry; ranks below the flags");
-    __shared__ uint32_t hist_[FINAL ? 1 : C::HW], cur_[FINAL ? 1 : C::HW]; // H16: two 16-bit counters per word
-    __shared__ HT base[FINAL ? 1 : C::NB];
-    __shared__ uint32_t wsum[NT / 64 + 1];
+    __shared__ __attribute__((aligned(16))) uint8_t un[G::UN_BYTES];
+    __shared__ typename G::Hist hist_, cur_;                   // H16: two 16-bit counters per word
+    __shared__ typename G::Base base;
+    __shared__ typename G::Wsum wsum;
     __shared__ uint32_t ghist[CARRY ? C::NB : 1], gbase[CARRY ? C::NB : 1]; // the generation waves' tables
     __shared__ uint64_t gr0p[CARRY ? 16 : 1];
     uint16_t* sidx = reinterpret_cast<uint16_t*>(un); // slot round: ktab[key][rank], the row ids of each key
     uint16_t* ktab = sidx;
-    uint32_t* bend = reinterpret_cast<uint32_t*>(un + (SLOT ? un_slot_bend<C>() : un_walk_bend<C>(CAP)));
-    uint32_t* ovl = reinterpret_cast<uint32_t*>(un + un_slot_ovl<C>()); // slot round only
-    uint32_t* plist = reinterpret_cast<uint32_t*>(un + (SLOT ? un_slot_list<C>() : un_walk_list<C>(CAP)));
+    uint32_t* bend = reinterpret_cast<uint32_t*>(un + G::UN_BEND);
+    uint32_t* ovl = reinterpret_cast<uint32_t*>(un + G::UN_OVL); // slot round only
+    uint32_t* plist = reinterpret_cast<uint32_t*>(un + G::UN_PLIST);
     uint32_t* spair = FOLD ? plist : reinterpret_cast<uint32_t*>(un);
     const int tid = threadIdx.x;
-    const int G = gridDim.x;
+    const int grid = gridDim.x;
     int it = 0;
-    int bk = xcd_bucket<C::NB>(blockIdx.x, 0, G, nbk);
+    int bk = xcd_bucket<C::NB>(blockIdx.x, 0, grid, nbk);
     if (bk < 0) return; // uniform per workgroup
     if constexpr (CARRY) {
         // the role is wave-uniform: a scalar branch
@@ -772,6 +914,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         }
     };
     // rows i and j share a parent (depth-1 duplicate): equal producing bucket and a common LDS row
+    // (keep in step with eh_shares_parent above, which eh_final_candidates uses)
     auto shares_parent = [&](uint32_t i, uint32_t j) -> bool {
         const uint32_t a = psig[i], b = psig[j];
         const uint32_t ai = a & C::IMASK, bi = b & C::IMASK;
@@ -816,6 +959,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         return keep;
     };
 
+    // (keep in step with the free opaque_tid() above, which the phase functions use)
     // A thread id the compiler cannot see through: keeps the per-lane index math of the
     // prefetch/commit loops from being hoisted out of the persistent loop (live invariants
     // would otherwise push the prefetched rows out to scratch).
@@ -825,7 +969,6 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
         return t;
     };
     // (a round that does not prune loads only the row words of each slot)
-    constexpr int LWI = PRUNE ? (CPI ? WI + 1 : WI + 2) : WI;
     uint32_t nr[RPL][LWI];
     uint32_t krank[FOLD ? RPL : 1]; // FOLD: (key << 16) | rank in the key group of each committed row
     int pf_bk = bk;
@@ -835,17 +978,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     // which the descriptor's range check drops), so the compiler can count the outstanding
     // operations and wait for the prefetched words with a precise vmcnt(N) instead of vmcnt(0): a
     // vmcnt(0) at the commit would wait for the acks of the previous bucket's emit stores as well.
-    auto issue = [&](int u0, int u1) {
-        const int nonce = pf_bk / C::NB, d = pf_bk % C::NB;
-        const auto rs = buf_rsrc(Rin + ((size_t)nonce * C::ROWS + (size_t)d * C::AREA) * SWI, CAP * SWI * 4);
-        const uint32_t ot = opaque_tid();
-#pragma unroll
-        for (int u = 0; u < RPL; ++u) {
-            if (u < u0 || u >= u1) continue;
-            const uint32_t r = ot + u * NT;
-            row_load<LWI>(rs, r < pf_n ? r * (SWI * 4) : OOB, nr[u]);
-        }
-    };
+    auto issue = [&](int u0, int u1) { eh_prefetch<G>(Rin, pf_bk, pf_n, u0, u1, nr); };
 
     // prologue: first bucket in flight, fill of the second known
     uint32_t fill = CTRin[bk]; // rows offered to the current bucket (more than CAP: the rest were dropped)
@@ -878,7 +1011,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
     // slot round: overflow rows of this workgroup's buckets of the current nonce and the most in one
     // bucket (uniform), written to the nonce's counters when the nonce changes
     uint32_t ovf_sum = 0, ovf_max = 0;
-    const int bk1 =xcd_bucket<C::NB>(blockIdx.x, 1, G, nbk);
+    const int bk1 =xcd_bucket<C::NB>(blockIdx.x, 1, grid, nbk);
     uint32_t fill_next = bk1 >= 0 ? CTRin[bk1] : 0u;
     // Fill of bucket b (0 for b < 0). As a buffer load it is counted by vmcnt, which barriers do not
     // drain; a plain load of this uniform address would be a scalar load, counted with the LDS
@@ -946,99 +1079,54 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             for (int k = tid; k < C::NRESTS; k += NT) bend[k] = 0;
         if (tid == 0) npairs = 0;
         EH_STAMP(1);
-        const int bn = xcd_bucket<C::NB>(blockIdx.x, it + 1, G, nbk);
+        const int bn = xcd_bucket<C::NB>(blockIdx.x, it + 1, grid, nbk);
         const bool more = bn >= 0; // uniform
         const uint32_t fn = more ? (uint32_t)__builtin_amdgcn_readfirstlane(fill_next) : 0u;
         const uint32_t nn = min(fn, (uint32_t)CAP);
         pf_bk = more ? bn : bk;
         pf_n = nn;
-        const int bn2 = xcd_bucket<C::NB>(blockIdx.x, it + 2, G, nbk);
+        const int bn2 = xcd_bucket<C::NB>(blockIdx.x, it + 2, grid, nbk);
         issue(0, SLI); // nothing moves when !more (pf_n = 0), but the instruction count stays fixed
         fill_next = fill_of(bn2);
         eh_bar<1, NBAR>();
         EH_STAMP(2);
 
-        // D1. key sort. FOLD: the commit counted the keys; scan to group starts and place each
-        //     row by its rank: sorted position (krank, reused) and the number of later positions
-        //     in the row's key group (its pairs, capped at 14 as below). Final round: count,
-        //     scan, then place (sidx = row ids grouped by key, bend[key] = end of the key's group).
-        auto key_of = [&](uint32_t i) -> uint32_t { return rows[i * WI] >> (32 - C::RB); };
+        // D1. key sort (eh_key_sort); a slot round has none
         uint32_t kpairs[FOLD ? RPL : 1];
         if constexpr (SLOT) {
-            // no key sort: the commit filed every row under its key. The phase reads as 0 cycles.
+            // the commit filed every row under its key. The phase reads as 0 cycles.
             if constexpr (STAMP) {
                 if (threadIdx.x == 0) stamps[(size_t)bk * 16 + 3] = stamps[(size_t)bk * 16 + 2];
             }
             issue(SLI, 2 * SLI);
-        } else if constexpr (FOLD) {
-            EH_BAR_SCAN(2, NBAR); // barriers 2, 3
-            block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
-            const uint32_t ot = opaque_tid();
-#pragma unroll
-            for (int u = 0; u < RPL; ++u) {
-                const uint32_t r = ot + u * NT;
-                kpairs[u] = 0;
-                if (r < n) {
-                    const uint32_t key = krank[u] >> 16;
-                    const uint32_t pos = bend[key] + (krank[u] & 0xffff);
-                    const uint32_t e = key + 1 < (uint32_t)C::NRESTS ? bend[key + 1] : n;
-                    sidx[pos] = (uint16_t)r;
-                    krank[u] = pos;
-                    kpairs[u] = min(e - pos - 1, 14u);
-                    if (e - pos - 1 > 14u) atomicAdd(&pdrop[nonce * PDW + STAGE], e - pos - 1 - 14u); // capped pairs (rare) count as pair-list drops
-                }
-            }
         } else {
-            for (uint32_t i = tid; i < n; i += NT) atomicAdd(&bend[key_of(i)], 1u);
-            __syncthreads();
-            block_exscan<NT, (C::NRESTS + NT - 1) / NT>(bend, C::NRESTS, wsum);
-            for (uint32_t i = tid; i < n; i += NT) sidx[atomicAdd(&bend[key_of(i)], 1u)] = (uint16_t)i;
-        }
-        if constexpr (!SLOT) {
+            eh_key_sort<G>(rows, bend, sidx, wsum, pdrop, nonce, n, krank, kpairs);
             issue(SLI, 2 * SLI);
             eh_bar<4, NBAR>();
             EH_STAMP(3);
         }
 
         if constexpr (FINAL) {
-            // D2 (final round). Candidates are pairs equal on ALL remaining bits: each sorted
-            // position scans the rest of its key group (a few rows). No pair list, so a bucket's
-            // pair count is not capped (a capped list here silently lost solutions).
-            static_assert(WI == 1, "final-round rows are one word");
-            for (uint32_t p = tid; p < n; p += NT) {
-                const uint32_t i = sidx[p], ri = rows[i], e = bend[ri >> (32 - C::RB)];
-                for (uint32_t q = p + 1; q < e; ++q) {
-                    const uint32_t j = sidx[q];
-                    if ((rows[j] ^ ri) & ~RMI) continue;
-                    if constexpr (PRUNE) {
-                        if (shares_parent(i, j)) continue;
-                    }
-                    const uint32_t c = atomicAdd(&ncand[nonce], 1u);
-                    if (c < (uint32_t)C::MAXCAND) cand[(size_t)nonce * C::MAXCAND + c] = pack_tri(d, i, j);
-                }
-            }
+            // D2, final round
+            eh_final_candidates<G>(rows, psig, pdw, sidx, bend, ncand, cand, nonce, d, n);
             issue(2 * SLI, RPL);
         } else {
-            // D2. pair list by per-wave compaction. Sorted position p pairs with every later
-            //     position of its key group: c_p = bend[key] - p - 1 pairs (capped at 14; a group
-            //     of 16+ rows is ~1e-8 likely). Each lane counts the pairs of the rows it
-            //     committed (from registers), a DPP wave scan gives the lane's offset inside its
-            //     wave, ONE LDS atomic per wave claims the wave's block of the list, and the lane
-            //     writes its (j << 16 | i) pairs there: one barrier. The list holds MP*NT pairs
-            //     (above the row capacity: capped pair lists lost ~9% of the solutions); identical
-            //     subtrees and pairs that share a parent are dropped when the pairs are read back.
-            //     Slot round: a row of rank t in its key group pairs with the rows of smaller rank.
-            //     min(t, 8) of them are the first slots of ktab[key], one 16-byte LDS read, written
-            //     out by a short loop that selects the word in registers (BCP_EH_SLOT_LIST). A row on
-            //     the overflow list (0.6 per bucket) is listed by lane `ordinal`, not its own: all eight table rows, and
-            //     the list entries of its key with a smaller ordinal, at most 6 (the 14-partner cap).
-            //     Every unordered pair of a key group is so listed once, whatever order the atomics
-            //     took. Only when more than OVL rows were offered to the list (never seen) pairs
-            //     among overflow rows are lost; they are counted exactly: every overflow row adds
-            //     its t - 8, every list lane takes off the pairs it lists.
-            uint32_t cnt = 0;
-            uint32_t le = 0, lm = 0, ln = 0; // slot round: this lane's list entry, its partners on the list, its pairs
+            // D2. pair list by per-wave compaction (eh_list_claim): one barrier. The sorted round's
+            //     form is eh_list_sorted; the slot round's stays inline here (as a function it cost
+            //     three VGPRs in (200,9) round 5, profiles/equihash_r11.md).
             if constexpr (SLOT) {
+                // Slot round: a row of rank t in its key group pairs with the rows of smaller rank.
+                // min(t, 8) of them are the first slots of ktab[key], one 16-byte LDS read, written
+                // out by a short loop that selects the word in registers (eight predicated stores
+                // lost 0.7% Sol/s, profiles/equihash_r10.md). A row on the overflow list (0.6 per
+                // bucket) is listed by lane `ordinal`, not its own: all eight table rows, and the
+                // list entries of its key with a smaller ordinal, at most 6 (the 14-partner cap).
+                // Every unordered pair of a key group is so listed once, whatever order the atomics
+                // took. Only when more than OVL rows were offered to the list (never seen) pairs
+                // among overflow rows are lost; they are counted exactly: every overflow row adds
+                // its t - 8, every list lane takes off the pairs it lists.
+                uint32_t cnt = 0;
+                uint32_t le = 0, lm = 0, ln = 0; // this lane's list entry, its partners on the list, its pairs
                 const uint32_t nov = __builtin_amdgcn_readfirstlane(novf);
                 const uint32_t NO = min(nov, (uint32_t)OVL);
                 const bool full = nov > (uint32_t)OVL; // uniform
@@ -1066,28 +1154,21 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     ln = 8u + lm;
                     cnt = ln;
                 }
-            }
+                // (the per-wave claim of eh_list_claim, deliberately written out: keep in step)
 #pragma unroll
-            for (int u = 0; u < RPL; ++u) cnt += kpairs[u];
-            const uint32_t incl = wave_incl<false>(cnt);
-            uint32_t wb = 0;
-            if ((tid & 63) == 63) wb = atomicAdd(&npairs, incl);
-            uint32_t o = __builtin_amdgcn_readlane(wb, 63) + incl - cnt;
-            if constexpr (SLOT) {
+                for (int u = 0; u < RPL; ++u) cnt += kpairs[u];
+                const uint32_t incl = wave_incl<false>(cnt);
+                uint32_t wb = 0;
+                if ((tid & 63) == 63) wb = atomicAdd(&npairs, incl);
+                uint32_t o = __builtin_amdgcn_readlane(wb, 63) + incl - cnt;
                 // the first c rows of `key`'s slots as partners of row i, at plist[o..]
                 auto table_pairs = [&](uint32_t key, uint32_t c, uint32_t i) {
                     const u4v w = *reinterpret_cast<const u4v*>(&ktab[key * 8]);
                     const uint32_t room = o < (uint32_t)(MP * NT) ? (uint32_t)(MP * NT) - o : 0u;
                     const uint32_t ce = min(c, room);
-                    if constexpr (BCP_EH_SLOT_LIST == 1) { // a short loop with a register select
-                        for (uint32_t q = 0; q < ce; ++q) {
-                            const uint32_t ww = q < 4 ? (q < 2 ? w.x : w.y) : (q < 6 ? w.z : w.w);
-                            plist[o + q] = ((q & 1) ? (ww & 0xffff0000u) : (ww << 16)) | i;
-                        }
-                    } else { // eight predicated stores
-#pragma unroll
-                        for (int q = 0; q < 8; ++q)
-                            if ((uint32_t)q < ce) plist[o + q] = ((q & 1) ? (w[q >> 1] & 0xffff0000u) : (w[q >> 1] << 16)) | i;
+                    for (uint32_t q = 0; q < ce; ++q) { // a short loop with a register select
+                        const uint32_t ww = q < 4 ? (q < 2 ? w.x : w.y) : (q < 6 ? w.z : w.w);
+                        plist[o + q] = ((q & 1) ? (ww & 0xffff0000u) : (ww << 16)) | i;
                     }
                     o += c;
                 };
@@ -1105,16 +1186,7 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
                     }
                 }
             } else {
-#pragma unroll
-            for (int u = 0; u < RPL; ++u) {
-                if (!kpairs[u]) continue;
-                const uint32_t p = krank[u];
-                const uint32_t i = tid + u * NT;
-                for (uint32_t q = p + 1; q <= p + kpairs[u]; ++q, ++o) {
-                    if (o >= (uint32_t)(MP * NT)) continue;
-                    plist[o] = ((uint32_t)sidx[q] << 16) | i;
-                }
-            }
+                eh_list_sorted<G>(sidx, plist, npairs, krank, kpairs);
             }
             eh_bar<BAR.list, NBAR>();
             EH_STAMP(7); // pair list complete (splits D2 into listing and filtering)
@@ -1185,8 +1257,6 @@ void eh_round(const uint32_t* __restrict__ Rin, const uint32_t* __restrict__ CTR
             EH_STAMP(5);
             // D4. emit, one lane per output row in destination order: XOR, shift one digit,
             //     store into the claimed run (rows past the next round's capacity are dropped)
-            constexpr uint32_t OCAP = C::cap(STAGE + 1 <= C::K ? STAGE + 1 : C::K);
-            constexpr uint32_t RMO = C::rmask(STAGE);
             const auto rs_out = buf_rsrc(Rout + (size_t)nonce * C::ROWS * SWO, (uint32_t)(C::ROWS * SWO * 4));
             const auto rs_p = buf_rsrc(Pout + (TPO ? ((size_t)nonce * C::NB + d) * PTW : 0), TPO ? PTW * 4 : 0);
 #pragma unroll
@@ -1465,13 +1535,14 @@ struct EquihashGpuSolver::Impl {
     // Kernel eh_round<C, S, STAMP, CARRY> over the group of `gn` nonces that starts at nonce `noff`.
     // CARRY: the round carries the generation of the next group's first `next` nonces.
     template <class C, int S, bool STAMP, bool CARRY> void launch_round_as(int noff, int gn, int next) {
-        constexpr bool OUT = S < C::K;        // the final round writes candidates, no stage
-        constexpr int SO = S < C::K ? S : 0;  // the output stage
-        constexpr bool TP = OUT && C::tp(SO); // the output stage's parent tables
+        using G = bcpk::EhRoundGeom<C, S, CARRY>;
+        constexpr bool OUT = !G::FINAL;       // the final round writes candidates, no stage
+        constexpr int SO = OUT ? S : 0;       // the output stage
+        constexpr bool TP = G::TPO;           // the output stage's parent tables
         constexpr size_t PDW = C::PDW;
         const size_t o = (size_t)noff;
-        const uint32_t* rin = d_rst[S - 1].p + o * C::ROWS * C::sw(S - 1);
-        uint32_t* rout = OUT ? d_rst[SO].p + o * C::ROWS * C::sw(SO) : nullptr;
+        const uint32_t* rin = d_rst[S - 1].p + o * C::ROWS * G::SWI;
+        uint32_t* rout = OUT ? d_rst[SO].p + o * C::ROWS * G::SWO : nullptr;
         const uint32_t* cin = d_ctr.p + ((size_t)(S - 1) * batch + o) * C::NB;
         uint32_t* cout = OUT ? d_ctr.p + ((size_t)S * batch + o) * C::NB : nullptr;
         uint32_t* pout = TP ? d_ptab[SO].p + o * C::NB * C::ptab(SO) : nullptr;
@@ -1690,13 +1761,12 @@ struct EquihashGpuSolver::Impl {
                 stats.stage_dropped_all[s] += q[K + 1 + s];
                 stats.stage_dropped_nonce[nn] += q[K + 1 + s];
             }
-            if constexpr (C::PDW > 2 * C::K + 2) { // slot rounds: rows past the key slots, and the most in one bucket
-                stats.overflow_rows_all.resize(K + 1, 0);
-                stats.overflow_bucket_max.resize(K + 1, 0);
-                for (size_t r = 1; r <= K; ++r) {
-                    stats.overflow_rows_all[r] += q[2 * K + 1 + r];
-                    stats.overflow_bucket_max[r] = std::max<uint64_t>(stats.overflow_bucket_max[r], q[3 * K + 1 + r]);
-                }
+            // slot rounds: rows past the key slots, and the most in one bucket
+            stats.overflow_rows_all.resize(K + 1, 0);
+            stats.overflow_bucket_max.resize(K + 1, 0);
+            for (size_t r = 1; r <= K; ++r) {
+                stats.overflow_rows_all[r] += q[2 * K + 1 + r];
+                stats.overflow_bucket_max[r] = std::max<uint64_t>(stats.overflow_bucket_max[r], q[3 * K + 1 + r]);
             }
         }
         if (debug) stats.pair_dropped = pd;

@@ -50,8 +50,8 @@ struct EhGpuStats {
     std::vector<uint64_t> pair_dropped;
     std::vector<uint64_t> stage_dropped_all;  // every nonce: rows past a round's capacity per stage (accumulated)
     std::vector<uint64_t> pair_dropped_all;   // every nonce: pairs past a round's pair list, per round (accumulated)
-    // slot rounds (BCP_EH_KEY_SLOTS), every nonce, per round: rows that found their key's slots taken
-    // (accumulated), and the most of them in one bucket; empty in a build without slot rounds
+    // slot rounds (EhCfg::ks), every nonce, per round: rows that found their key's slots taken
+    // (accumulated), and the most of them in one bucket (index = round; zero for the sorted rounds)
     std::vector<uint64_t> overflow_rows_all, overflow_bucket_max;
     std::vector<uint64_t> pair_dropped_nonce;  // last batch, per nonce: pairs dropped in all rounds
     std::vector<uint64_t> stage_dropped_nonce; // last batch, per nonce: rows dropped in all stages

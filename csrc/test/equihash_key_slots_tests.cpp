@@ -1,4 +1,4 @@
-// equihash_key_slots_tests: the slot rounds of the Equihash solver (EhCfg::ks, BCP_EH_KEY_SLOTS) as
+// equihash_key_slots_tests: the slot rounds of the Equihash solver (EhCfg::ks) as
 // csrc/kernels/equihash_layout.h describes them: which rounds keep key slots instead of the key
 // sort, their LDS bytes (pinned to what the compiler reports for eh_round<Cfg200_9, S, *, CARRY>,
 // profiles/raw/r10/resources.md), the workgroup barriers per bucket of either round variant, the
@@ -23,8 +23,6 @@ template <class C> std::vector<int> SlotRounds() {
 }
 
 } // namespace
-
-#if BCP_EH_KEY_SLOTS
 
 TEST_CASE(equihash_key_slots_tests, slot_rounds) {
     // (200,9): rounds 3..8; 1 and 2 would need ~174 KB of LDS, the final round keeps the sort
@@ -86,8 +84,6 @@ TEST_CASE(equihash_key_slots_tests, union_layout) {
     CHECK(Cfg96_5::AREA_NF < 0x4000);
 }
 
-#endif // BCP_EH_KEY_SLOTS
-
 // The barriers of a bucket iteration: one constant per round variant, which the round waves and
 // the generation waves both take from eh_bars.
 TEST_CASE(equihash_key_slots_tests, barriers) {
@@ -109,7 +105,7 @@ TEST_CASE(equihash_key_slots_tests, barriers) {
 TEST_CASE(equihash_key_slots_tests, counters) {
     using C = Cfg200_9;
     // [1..K] pair drops, [K+1..2K] row drops; slot rounds add [2K+2..3K+1] and [3K+2..4K+1]
-    CHECK_EQ(C::PDW, BCP_EH_KEY_SLOTS ? 4 * C::K + 2 : 2 * C::K + 2);
-    CHECK_EQ(Cfg96_5::PDW, BCP_EH_KEY_SLOTS ? 4 * 5 + 2 : 2 * 5 + 2);
-    if (BCP_EH_KEY_SLOTS) CHECK(3 * C::K + 1 + C::K < C::PDW); // the last round's bucket maximum is inside
+    CHECK_EQ(C::PDW, 4 * C::K + 2);
+    CHECK_EQ(Cfg96_5::PDW, 4 * 5 + 2);
+    CHECK(3 * C::K + 1 + C::K < C::PDW); // the last round's bucket maximum is inside
 }

@@ -2,13 +2,15 @@
 // checked on the host for the three configurations: slot widths and padding bits, the stages with
 // table parents, the parent decoders against slots built as the rounds' emit builds them, the
 // pair-table and LDS sizes (pinned to what the compiler reports for the round kernels,
-// profiles/raw/r9/resources.md) and the coverage of the carried generation.
+// profiles/raw/r9/resources.md), the per-instantiation geometry (EhRoundGeom) against the functions
+// it gathers, and the coverage of the carried generation.
 #include "test/unittest.h"
 
 #include "kernels/equihash_layout.h"
 
 #include <random>
 #include <set>
+#include <utility>
 
 namespace {
 
@@ -147,7 +149,61 @@ template <class C> void CheckSizes() {
     }
 }
 
+// EhRoundGeom<C, S, CARRY> against the functions it gathers
+template <class C, int S, bool CARRY> void CheckGeom() {
+    using G = EhRoundGeom<C, S, CARRY>;
+    CHECK_EQ(G::FINAL, S == C::K);
+    CHECK_EQ(G::WI, C::words(S - 1));
+    CHECK_EQ(G::WO, S < C::K ? C::words(S) : 1);
+    CHECK_EQ(G::CAP, C::cap(S));
+    CHECK_EQ(G::PRUNE, round_prunes<C>(S, CARRY));
+    CHECK_EQ(G::SLOT, C::ks(S) > 0);
+    CHECK_EQ(G::NBAR, eh_bars(G::SLOT).n);
+    CHECK_EQ(G::BAR.list, eh_bars(G::SLOT).list);
+    CHECK_EQ(G::BAR.sort, eh_bars(G::SLOT).sort);
+    CHECK_EQ(G::NT, round_nt<C>(S, CARRY));
+    CHECK_EQ(G::MP, round_mp<C>(S, CARRY));
+    CHECK_EQ(G::RPL, (C::cap(S) + G::NT - 1) / G::NT);
+    CHECK_EQ(G::SLI, (G::RPL + BCP_EH_PF_SLICES - 1) / BCP_EH_PF_SLICES);
+    CHECK_EQ(G::BPT, (C::NB + G::NT - 1) / G::NT);
+    CHECK_EQ(G::SWI, C::sw(S - 1));
+    CHECK_EQ(G::SWO, S < C::K ? C::sw(S) : 1);
+    CHECK_EQ(G::TPO, S < C::K && C::tp(S));
+    CHECK_EQ(G::PTW, G::TPO ? C::ptab(S) : 1);
+    CHECK_EQ(G::CPI, C::cp(S - 1));
+    CHECK_EQ(G::RMI, C::rmask(S - 1));
+    CHECK_EQ(G::RMO, C::rmask(S));
+    CHECK_EQ(G::OCAP, (uint32_t)C::cap(S < C::K ? S + 1 : C::K));
+    CHECK_EQ(G::LWI, G::WI + (G::PRUNE ? (G::CPI ? 1 : 2) : 0));
+    CHECK_EQ(sizeof(typename G::HT), C::H16 ? 2u : 4u);
+    CHECK_EQ(G::UN_BYTES, G::SLOT ? slot_un<C>(S, CARRY) : round_un<C>(S, CARRY));
+    CHECK_EQ(G::UN_BEND, G::SLOT ? un_slot_bend<C>() : un_walk_bend<C>(C::cap(S)));
+    CHECK_EQ(G::UN_OVL, un_slot_ovl<C>());
+    CHECK_EQ(G::UN_PLIST, G::SLOT ? un_slot_list<C>() : un_walk_list<C>(C::cap(S)));
+    CHECK_EQ(G::LDS_BYTES, G::SLOT ? slot_lds<C>(S, G::PRUNE, CARRY) : round_lds<C>(S, G::PRUNE, CARRY));
+    // the LDS arrays the kernel declares add up to LDS_BYTES (rows rounded to 16 bytes, pdw to 4; a
+    // final round keeps one-word placeholders the compiler drops; a carrying slot round rounds to 8)
+    if (S < C::K) {
+        const int gen = CARRY ? 2 * C::NB * 4 + 16 * 8 : 0;
+        const int sum = (int)sizeof(typename G::Rows) + (G::PRUNE ? (int)sizeof(typename G::Psig) : 0) +
+                        (G::PRUNE && !G::CPI ? ((int)sizeof(typename G::Pdw) + 3) / 4 * 4 : 0) + 4 + (G::SLOT ? 4 : 0) +
+                        G::UN_BYTES + 2 * (int)sizeof(typename G::Hist) + ((int)sizeof(typename G::Base) + 3) / 4 * 4 +
+                        (int)sizeof(typename G::Wsum) + gen;
+        CHECK_EQ(G::SLOT && CARRY ? (sum + 7) / 8 * 8 : sum, G::LDS_BYTES);
+    }
+}
+template <class C, int... S> void CheckGeoms(std::integer_sequence<int, S...>) {
+    (CheckGeom<C, S + 1, false>(), ...);
+    if constexpr (C::GW > 0) ((S + 1 < C::K ? CheckGeom<C, (S + 1 < C::K ? S + 1 : 1), true>() : void()), ...);
+}
+
 } // namespace
+
+TEST_CASE(equihash_layout_tests, round_geometry) {
+    CheckGeoms<Cfg200_9>(std::make_integer_sequence<int, Cfg200_9::K>{});
+    CheckGeoms<Cfg96_5>(std::make_integer_sequence<int, Cfg96_5::K>{});
+    CheckGeoms<Cfg48_5>(std::make_integer_sequence<int, Cfg48_5::K>{});
+}
 
 TEST_CASE(equihash_layout_tests, slot_widths) {
     CheckSlotWidths<Cfg200_9>();

@@ -1,4 +1,4 @@
-"""Equihash GPU solver: the "slot rounds" (EhCfg::ks, BCP_EH_KEY_SLOTS).
+"""Equihash GPU solver: the "slot rounds" (EhCfg::ks).
 
 Rounds 3-8 of (200,9) and every collision round of (96,5) have no key sort: the commit writes each
 row's id into slot `rank` of its key (8 slots per key), a row then reads all its partners with one
@@ -6,9 +6,6 @@ row's id into slot `rank` of its key (8 slots per key), a row then reads all its
 1-2 of (200,9), the final rounds and (48,5) keep the sort. Plain and carrying kernels are separate
 instantiations, so both run here, and `overflow_rows_all` (rows that went through the list, per
 round) shows that the overflow path ran: about a seventh of the solutions pass through such a row.
-
-In a build with BCP_EH_KEY_SLOTS=0 `overflow_rows_all` is empty and the overflow assertions fail:
-these tests are about the default build.
 """
 import concurrent.futures as cf
 import struct

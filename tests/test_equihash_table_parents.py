@@ -5,9 +5,6 @@ the producing bucket d in its padding bits, the (j << 16 | i) word of output ord
 pair table P[stage][nonce][d][t], and a run-base table B[stage][nonce][d][b] turns a slot's
 position in area b back into t. Only the tree expansion and DebugDump read P and B. (96,5) and
 (48,5) prune from round 2 and never use the layout, so every case here is (200,9) at tiny batches.
-
-With BCP_EH_TABLE_PARENTS=0 the slots keep their parent words; everything here holds for that
-build too, except the two debug_expand_corrupt modes, which exist only for a table stage.
 """
 import concurrent.futures as cf
 import struct
