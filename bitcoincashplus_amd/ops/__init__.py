@@ -33,6 +33,7 @@ Kernel map (reference hot loops):
   hash160            K11 RIPEMD160(SHA256(m)) of byte strings         wallet_match.hip
   wallet_match       K12 txids, prevouts, scripts against the wallet's match table  wallet_match.hip
   wallet_scan        K12 a transaction list against a wallet, exact  wallet_match.hip + wallet/walletscan.cpp
+  coin_select        K13 the wallet's subset search, one lane per trial  coin_select.hip + wallet/coinselect.cpp
   Equihash solving (K1-K3) is ``models.EquihashModel.gpu_solver``.
 """
 from __future__ import annotations
@@ -220,7 +221,7 @@ def equihash_mine(n: int, k: int, prefix108, nonce_first, count: int, target, ba
 
 __all__ = ["sha256d64", "sha256d_batch", "merkle_root", "scan_nonces", "equihash_verify", "ecdsa_verify",
            "ecdsa_verify_compact", "short_txids", "verify_forkid", "equihash_pow_check", "equihash_mine", "check_headers",
-           "bloom_match", "bloom_scan", "hash160", "wallet_match", "wallet_scan"]
+           "bloom_match", "bloom_scan", "hash160", "wallet_match", "wallet_scan", "coin_select"]
 
 
 def short_txids(k0: int, k1: int, txids, device: int = -1) -> list:
@@ -403,3 +404,48 @@ def wallet_scan(txs, wallet_desc: dict, use_gpu: bool = True, f_update: bool = T
     if use_gpu:
         require_gpu("wallet_scan")
     return native.wallet_scan([bytes(t) for t in txs], wallet_desc, use_gpu, f_update)
+
+
+def coin_select(values, target: int, trials: int = 1000, seed=(0, 0), both_runs: bool = False, use_gpu: bool = True,
+                device: int = -1, run: int = 0, min_change: int | None = None):
+    """The stochastic subset search of the wallet's coin selection (csrc/kernels/coin_select.h), one
+    lane per trial: the smallest (total, trial, pass, index) with total >= `target` that `trials`
+    (1..65536) trials reach over `values` (amounts > 0, sorted descending, sum below 2^63) under
+    the 128-bit `seed` (k0, k1). `run` (0 or 1) picks the run's random stream. ``both_runs=True``
+    searches run 0 at `target` and run 1 at `target + min_change` (the wallet's MIN_CHANGE by
+    default) in one launch and returns a list of the two results.
+
+    Host path: `values` is a list of ints or a CPU tensor; a result is (total, trial, pass, index,
+    included coin indices), or None when the values sum to less than the target.
+    ``use_gpu=False`` runs the CPU twin, which gives the same tuple.
+
+    Device-resident path: `values` is a ``torch.int64`` GPU tensor. The kernels are enqueued on
+    the current torch stream and the result is an int64 GPU tensor [4] (or [2, 4] with
+    ``both_runs``) of (total, trial, pass, index), all -1 for no candidate; nothing synchronises
+    and the amounts are not checked."""
+    k0, k1 = (int(x) & 0xFFFFFFFFFFFFFFFF for x in seed)
+    if min_change is None:
+        min_change = native.COIN_SELECT_MIN_CHANGE
+    if both_runs and run != 0:
+        raise ValueError("coin_select: both_runs starts at run 0")
+    targets = [int(target), int(target) + int(min_change)] if both_runs else [int(target)]
+    if _on_gpu(values):
+        require_gpu("coin_select")
+        if not use_gpu:
+            raise ValueError("coin_select: GPU tensor with use_gpu=False")
+        if values.dtype != torch.int64:
+            raise TypeError("coin_select: expected a torch.int64 tensor")
+        x = values.detach().contiguous().view(-1)
+        out = torch.empty((len(targets), 4), dtype=torch.int64, device=x.device)
+        scratch = torch.empty(native.coin_select_scratch_bytes(trials, len(targets)) // 8, dtype=torch.int64,
+                              device=x.device)
+        dev, stream = _dev_stream(x)
+        native.coin_select_device(x.data_ptr(), x.numel(), targets, run, trials, k0, k1, scratch.data_ptr(),
+                                  out.data_ptr(), dev, stream)
+        return out if both_runs else out[0]
+    if use_gpu:
+        require_gpu("coin_select")
+    if torch is not None and isinstance(values, torch.Tensor):
+        values = values.tolist()
+    res = native.coin_select([int(v) for v in values], targets, run, trials, k0, k1, use_gpu, device)
+    return list(res) if both_runs else res[0]

@@ -290,6 +290,21 @@ private:
 void WalletMatchBatch(const WalletMatchTableDesc& table, const uint8_t* kinds, const unsigned char* blob, size_t blobBytes,
                       const uint32_t* offs, const uint32_t* lens, size_t n, std::vector<uint8_t>& flags, int device = -1);
 
+// --------------------------------------------------------------- wallet: coin selection
+// The stochastic subset search of kernels/coin_select.h on the device, one lane per trial: the
+// smallest candidate (total, trial, pass, coin) of `trials` (1..65536) trials over n amounts (each
+// > 0, sum below 2^63, sorted descending by the caller) under the seed (k0, k1). nRuns = 1
+// searches run firstRun (0 or 1) at targets[0]; nRuns = 2 (firstRun 0) searches run 0 at
+// targets[0] and run 1 at targets[1] in the same launch. A run without a candidate (the sum is
+// below its target) has every field -1.
+struct CoinSelectRun {
+    int64_t total, trial, pass, index;
+};
+// From host memory through the relay context's pinned staging: one H2D copy, two launches, one
+// D2H copy, then a wait. Throws std::invalid_argument on counts or amounts out of range.
+void CoinSelectBatch(const int64_t* values, size_t n, const int64_t* targets, unsigned firstRun, unsigned nRuns,
+                     uint32_t trials, uint64_t k0, uint64_t k1, CoinSelectRun* out, int device = -1);
+
 // --------------------------------------------------------------- secp256k1
 // ECDSA verification batch: N jobs, msg32 = N*32 (big-endian digest bytes as signed),
 // sig64 = N*64 (r||s big-endian, s low-S-normalised, r,s in [1,n-1] checked on host),
@@ -342,6 +357,12 @@ void Hash160Device(const void* blob, size_t blobBytes, const void* offs, const v
 void WalletMatchDevice(const void* slots, uint32_t nSlots, uint64_t k0, uint64_t k1, bool hasWatch, uint32_t kindMask,
                        const void* kinds, const void* blob, size_t blobBytes, const void* offs, const void* lens,
                        void* flags, size_t n, int device, uintptr_t stream);
+// CoinSelectBatch on device memory: values = n int64 (8-byte aligned; the amounts cannot be
+// checked here), scratch = CoinSelectScratchBytes(trials, nRuns) bytes (8-byte aligned), out =
+// nRuns x 4 int64 (a CoinSelectRun each). targets is host memory.
+size_t CoinSelectScratchBytes(uint32_t trials, unsigned nRuns);
+void CoinSelectDevice(const void* values, size_t n, const int64_t* targets, unsigned firstRun, unsigned nRuns,
+                      uint32_t trials, uint64_t k0, uint64_t k1, void* scratch, void* out, int device, uintptr_t stream);
 // Device scratch the ECDSA kernels need per signature (the prep kernel's job records).
 size_t EcdsaJobBytes();
 // result[i] = 1 iff signature i verifies; inputs as EcdsaVerifyBatch (msg32 n x 32, sig64 compact

@@ -13,6 +13,7 @@
 #include "kernels/gpu_api.h"
 #include "kernels/hip_util.h"
 #include "kernels/relay_ctx.h"
+#include "kernels/siphash.h"
 
 #include <algorithm>
 #include <cstring>
@@ -21,16 +22,6 @@
 
 namespace bcpk {
 
-__device__ __forceinline__ uint64_t rotl64d(uint64_t x, int b) { return (x << b) | (x >> (64 - b)); }
-
-#define BCP_SIPROUND                                                                                   \
-    do {                                                                                               \
-        v0 += v1; v1 = rotl64d(v1, 13); v1 ^= v0; v0 = rotl64d(v0, 32);                                \
-        v2 += v3; v3 = rotl64d(v3, 16); v3 ^= v2;                                                      \
-        v0 += v3; v3 = rotl64d(v3, 21); v3 ^= v0;                                                      \
-        v2 += v1; v1 = rotl64d(v1, 17); v1 ^= v2; v2 = rotl64d(v2, 32);                                \
-    } while (0)
-
 __global__ __launch_bounds__(256) void shortid_kernel(uint64_t k0, uint64_t k1, const uint4* __restrict__ txids,
                                                       uint64_t* __restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -38,28 +29,13 @@ __global__ __launch_bounds__(256) void shortid_kernel(uint64_t k0, uint64_t k1, 
     const uint4 a = txids[2 * i], b = txids[2 * i + 1];
     const uint64_t d[4] = {((uint64_t)a.y << 32) | a.x, ((uint64_t)a.w << 32) | a.z, ((uint64_t)b.y << 32) | b.x,
                            ((uint64_t)b.w << 32) | b.z};
-    uint64_t v0 = 0x736f6d6570736575ULL ^ k0, v1 = 0x646f72616e646f6dULL ^ k1;
-    uint64_t v2 = 0x6c7967656e657261ULL ^ k0, v3 = 0x7465646279746573ULL ^ k1;
+    bcp::sip::Sip s;
+    s.Init(k0, k1);
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        v3 ^= d[w];
-        BCP_SIPROUND;
-        BCP_SIPROUND;
-        v0 ^= d[w];
-    }
-    const uint64_t t = 32ULL << 56; // message length 32 bytes, no tail bytes
-    v3 ^= t;
-    BCP_SIPROUND;
-    BCP_SIPROUND;
-    v0 ^= t;
-    v2 ^= 0xff;
-    BCP_SIPROUND;
-    BCP_SIPROUND;
-    BCP_SIPROUND;
-    BCP_SIPROUND;
-    out[i] = (v0 ^ v1 ^ v2 ^ v3) & 0xffffffffffffULL;
+    for (int w = 0; w < 4; ++w) s.Word(d[w]);
+    s.Word(32ULL << 56); // message length 32 bytes, no tail bytes
+    out[i] = s.Final() & 0xffffffffffffULL;
 }
-#undef BCP_SIPROUND
 
 // ------------------------------------------------------------------ K10 bloom membership
 constexpr uint32_t BLOOM_MAX_BYTES = 36000; // CBloomFilter::MAX_BLOOM_FILTER_SIZE

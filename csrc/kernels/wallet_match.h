@@ -12,6 +12,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "kernels/siphash.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define BCP_WM_HD __host__ __device__ __forceinline__
@@ -52,38 +54,9 @@ struct TableView {
     uint32_t hasWatch; // the table holds W entries
 };
 
-BCP_WM_HD uint64_t Rotl64(uint64_t x, int b) { return (x << b) | (x >> (64 - b)); }
+using sip::Rotl64;
+using sip::Sip; // SipHash-2-4 (kernels/siphash.h)
 BCP_WM_HD uint32_t Rotl32(uint32_t x, int b) { return (x << b) | (x >> (32 - b)); }
-
-struct Sip {
-    uint64_t v0, v1, v2, v3;
-    BCP_WM_HD void Init(uint64_t k0, uint64_t k1) {
-        v0 = 0x736f6d6570736575ULL ^ k0;
-        v1 = 0x646f72616e646f6dULL ^ k1;
-        v2 = 0x6c7967656e657261ULL ^ k0;
-        v3 = 0x7465646279746573ULL ^ k1;
-    }
-    BCP_WM_HD void Round() {
-        v0 += v1; v1 = Rotl64(v1, 13); v1 ^= v0; v0 = Rotl64(v0, 32);
-        v2 += v3; v3 = Rotl64(v3, 16); v3 ^= v2;
-        v0 += v3; v3 = Rotl64(v3, 21); v3 ^= v0;
-        v2 += v1; v1 = Rotl64(v1, 17); v1 ^= v2; v2 = Rotl64(v2, 32);
-    }
-    BCP_WM_HD void Word(uint64_t m) {
-        v3 ^= m;
-        Round();
-        Round();
-        v0 ^= m;
-    }
-    BCP_WM_HD uint64_t Final() {
-        v2 ^= 0xff;
-        Round();
-        Round();
-        Round();
-        Round();
-        return v0 ^ v1 ^ v2 ^ v3;
-    }
-};
 
 // Members sit at any byte offset: byte loads, never past the last byte.
 BCP_WM_HD uint32_t LoadLE32(const uint8_t* p) {

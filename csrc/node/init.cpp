@@ -12,6 +12,7 @@
 #include "node/sigverify.h"
 #include "net/blockencodings.h"
 #include "net/bloomscan.h"
+#include "wallet/coinselect.h"
 #include "wallet/walletscan.h"
 #include "rpc/httpserver.h"
 #include "rpc/server.h"
@@ -60,6 +61,7 @@ std::string HelpMessage() {
         {"-gpushortidthreshold=<n>", "Smallest mempool whose compact-block short ids are computed on the GPU (default: 16384)"},
         {"-gpubloomthreshold=<n>", "Smallest block or mempool (in transactions) matched against a peer's bloom filter on the GPU for merkleblock and mempool replies; 0 keeps them on the CPU (default: 0)"},
         {"-gpuwalletscanthreshold=<n>", "Smallest block (in transactions) whose transactions are matched against the wallet's keys and coins on the GPU during a rescan and when a block connects; 0 keeps the per-transaction loop (default: 250)"},
+        {"-gpucoinselectthreshold=<n>", "Smallest list of candidate coins whose subset search (sendtoaddress, sendmany, fundrawtransaction) runs on the GPU, one lane per trial; 0 keeps the serial loop (default: 2048)"},
         {"-gpudevices=<list>", "Comma-separated GPU indices the built-in Equihash miner runs on, one host thread per device (default: all visible)"},
         {"-gpuvalidationdevices=<list>", "Comma-separated GPU indices that verify block signatures and header solutions, one high-priority stream, service thread and host-fill worker group each; batches are sharded across them. When set, the built-in miner leaves these devices alone if others are available (default: every visible device, two lanes each)"},
         {"-maxsigcachesize=<n>", "Limit size of signature cache to <n> MiB (default: 32)"},
@@ -386,6 +388,8 @@ int AppMain(int argc, char* argv[]) {
     SetGpuBloomThreshold((size_t)std::max<int64_t>(0, gArgs.GetArg("-gpubloomthreshold", (int64_t)GetGpuBloomThreshold())));
     SetGpuWalletScanThreshold(
         (size_t)std::max<int64_t>(0, gArgs.GetArg("-gpuwalletscanthreshold", (int64_t)GetGpuWalletScanThreshold())));
+    SetGpuCoinSelectThreshold(
+        (size_t)std::max<int64_t>(0, gArgs.GetArg("-gpucoinselectthreshold", (int64_t)GetGpuCoinSelectThreshold())));
     if (gArgs.IsArgSet("-gpudevices")) {
         std::vector<int> devs;
         for (const std::string& tok : SplitString(gArgs.GetArg("-gpudevices", ""), ',')) {
@@ -418,6 +422,7 @@ int AppMain(int argc, char* argv[]) {
     const bool useGpu = gArgs.GetBoolArg("-gpu", true) && (GpuFaultInjection() || gpu::GpuAvailable());
     SetGpuBloomEnabled(useGpu);
     SetGpuWalletScanEnabled(useGpu);
+    SetGpuCoinSelectEnabled(useGpu);
     LogPrintf("GPU acceleration: %s%s\n", !useGpu ? "disabled" : gpu::GpuAvailable() ? gpu::DeviceName(0).c_str() : "none",
               GpuFaultInjection() ? " (fault injection: every GPU batch fails)" : "");
 

@@ -6,6 +6,8 @@
 #include "node/miner.h"
 #include "node/sigverify.h"
 #include "secp256k1/secp256k1.h"
+#include "wallet/coinselect.h"
+#include "wallet/wallet.h"
 
 namespace bcp {
 namespace py {
@@ -602,6 +604,60 @@ void bind_gpu(pyb::module_& m) {
         }
         return std::vector<bool>(r.begin(), r.end());
     });
+    // The wallet's subset search as a batch of trials (wallet/coinselect.h): per run (run
+    // first_run + i at targets[i]) a tuple (total, trial, pass, index, included coin indices), or
+    // None when the amounts sum to less than the target. use_gpu: the kernel, else its host twin.
+    m.def(
+        "coin_select",
+        [](const std::vector<int64_t>& values, const std::vector<int64_t>& targets, unsigned firstRun, uint32_t trials,
+           uint64_t k0, uint64_t k1, bool use_gpu, int device) {
+            if (targets.empty() || targets.size() > 2 || firstRun + targets.size() > 2)
+                throw std::invalid_argument("coin_select: runs are 0 and 1");
+            CoinSelectPick picks[2];
+            std::vector<uint32_t> in[2];
+            {
+                pyb::gil_scoped_release rel;
+                if (use_gpu) {
+                    CoinSelectGpu(values.data(), values.size(), targets.data(), firstRun, (unsigned)targets.size(), trials, k0,
+                                  k1, picks, device);
+                } else {
+                    for (size_t i = 0; i < targets.size(); ++i)
+                        picks[i] = CoinSelectCpu(values.data(), values.size(), targets[i], trials, k0, k1, firstRun + (unsigned)i);
+                }
+                for (size_t i = 0; i < targets.size(); ++i)
+                    in[i] = CoinSelectReplay(values.data(), values.size(), targets[i], k0, k1, firstRun + (unsigned)i, picks[i]);
+            }
+            pyb::list out;
+            for (size_t i = 0; i < targets.size(); ++i) {
+                if (picks[i].found) out.append(pyb::make_tuple(picks[i].total, picks[i].trial, picks[i].pass, picks[i].index, in[i]));
+                else out.append(pyb::none());
+            }
+            return out;
+        },
+        pyb::arg("values"), pyb::arg("targets"), pyb::arg("first_run"), pyb::arg("trials"), pyb::arg("k0"), pyb::arg("k1"),
+        pyb::arg("use_gpu") = true, pyb::arg("device") = -1);
+    m.def("coin_select_scratch_bytes", &gpu::CoinSelectScratchBytes, pyb::arg("trials"), pyb::arg("n_runs"));
+    m.def(
+        "coin_select_device",
+        [](uintptr_t values, size_t n, const std::vector<int64_t>& targets, unsigned firstRun, uint32_t trials, uint64_t k0,
+           uint64_t k1, uintptr_t scratch, uintptr_t out, int device, uintptr_t stream) {
+            if (targets.empty() || targets.size() > 2) throw std::invalid_argument("coin_select_device: one or two targets");
+            gpu::CoinSelectDevice(reinterpret_cast<const void*>(values), n, targets.data(), firstRun, (unsigned)targets.size(),
+                                  trials, k0, k1, reinterpret_cast<void*>(scratch), reinterpret_cast<void*>(out), device,
+                                  stream);
+        },
+        pyb::arg("values_ptr"), pyb::arg("n"), pyb::arg("targets"), pyb::arg("first_run"), pyb::arg("trials"), pyb::arg("k0"),
+        pyb::arg("k1"), pyb::arg("scratch_ptr"), pyb::arg("out_ptr"), pyb::arg("device"), pyb::arg("stream"));
+    m.def("coin_select_stats", []() {
+        const CoinSelectStats s = GetCoinSelectStats();
+        pyb::dict d;
+        d["gpu_selections"] = s.gpu_selections;
+        d["cpu_selections"] = s.cpu_selections;
+        d["gpu_failures"] = s.gpu_failures;
+        d["threshold"] = GetGpuCoinSelectThreshold();
+        return d;
+    });
+    m.attr("COIN_SELECT_MIN_CHANGE") = (int64_t)MIN_CHANGE;
     m.def("get_miner_gpu_devices", &GetMinerGpuDevices);
     m.def("set_miner_gpu_devices", &SetMinerGpuDevices);
     m.def("set_gpu_fault_injection", &SetGpuFaultInjection);

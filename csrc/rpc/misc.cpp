@@ -19,6 +19,7 @@
 #include "node/miner.h"
 #include "util/lockedpool.h"
 #include "util/strencodings.h"
+#include "wallet/coinselect.h"
 #include "wallet/walletscan.h"
 
 #include <mutex>
@@ -143,6 +144,14 @@ static UniValue getgpuinfo(const JSONRPCRequest& req) {
     wl.pushKV("gpu_failures", ws.gpu_failures);
     wl.pushKV("threshold", (uint64_t)GetGpuWalletScanThreshold());
     obj.pushKV("walletscan", wl);
+    // coin selections searched as a batch of trials (wallet/coinselect.h)
+    const CoinSelectStats cst = GetCoinSelectStats();
+    UniValue csl(UniValue::VOBJ);
+    csl.pushKV("gpu_selections", cst.gpu_selections);
+    csl.pushKV("cpu_selections", cst.cpu_selections);
+    csl.pushKV("gpu_failures", cst.gpu_failures);
+    csl.pushKV("threshold", (uint64_t)GetGpuCoinSelectThreshold());
+    obj.pushKV("coinselect", csl);
     // validation lanes (node/gpuverify.h): devices, stream priority, work done per lane
     GpuVerifyService& svc = GpuVerifyService::Instance();
     UniValue vd(UniValue::VARR);

@@ -32,6 +32,7 @@
 #include "util/lockedpool.h"
 #include "util/strencodings.h"
 #include "util/util.h"
+#include "wallet/coinselect.h"
 #include "wallet/wallet.h"
 #include "wallet/walletscan.h"
 
@@ -1644,6 +1645,70 @@ static bench::Reg reg_Wallet21k_100k_100("WalletScan_Block21k_Keys100k_Owned100"
 static bench::Reg reg_Wallet1k_1k_0("WalletScan_Block1k_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block1k", 1000, 1000, 0); });
 static bench::Reg reg_Wallet4k_1k_0("WalletScan_Block4k_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block4k", 4000, 1000, 0); });
 static bench::Reg reg_Wallet250_1k_0("WalletScan_Block250_Keys1k_Owned0", [](State& st) { WalletScanBench(st, "block250", 250, 1000, 0); });
+
+// SelectCoinsMinConf over a payout wallet's coins: seven in ten are equal coinbase-sized outputs,
+// the rest a spread of change, and the payment is a tenth of the balance with odd satoshis, so
+// every coin is a candidate and both subset searches run. Three arms alternate run by run in
+// this process: the reference's serial loop (what the wallet does below
+// -gpucoinselectthreshold), the batched search on its host twin, and the batched search on the
+// device, end to end with staging and copy-back (wallet/coinselect.h). At least 30 runs an arm.
+static void CoinSelectBench(State& st, size_t ncoins) {
+    if (!gpu::GpuAvailable()) return;
+    SelectParams("regtest");
+    CWallet wallet("bench", "", true);
+    std::vector<COutput> vCoins;
+    std::vector<std::unique_ptr<CWalletTx>> wtxs;
+    std::mt19937_64 rng(ncoins);
+    Amount balance = 0;
+    for (size_t i = 0; i < ncoins; i++) {
+        CMutableTransaction tx;
+        tx.nLockTime = (uint32_t)i;
+        tx.vout.resize(1);
+        tx.vout[0].nValue = i % 10 < 7 ? 1250000000LL : 100000 + (Amount)(rng() % 500000000ULL);
+        balance += tx.vout[0].nValue;
+        wtxs.emplace_back(new CWalletTx(&wallet, MakeTransactionRef(std::move(tx))));
+        wtxs.back()->fFromMe = true;
+        vCoins.push_back({wtxs.back().get(), 0, 6 * 24, true, true});
+    }
+    const Amount target = balance / 10 + 12345678;
+    const size_t keepThreshold = GetGpuCoinSelectThreshold();
+    static const char* const armName[3] = {"loop", "twin", "gpu"};
+    std::vector<double> ms[3];
+    Amount worst[3] = {0, 0, 0};
+    size_t iters = 0;
+    while (st.KeepRunning() || iters < 3 * 32) {
+        const int arm = (int)(iters % 3);
+        SetGpuCoinSelectThreshold(arm == 0 ? 0 : 1);
+        SetCoinSelectTwinOnly(arm == 1);
+        const CoinSelectStats before = GetCoinSelectStats();
+        std::set<std::pair<const CWalletTx*, unsigned int>> setCoinsRet;
+        Amount nValueRet = 0;
+        const int64_t t0 = GetTimeMicros();
+        const bool ok = wallet.SelectCoinsMinConf(target, 1, 6, 0, vCoins, setCoinsRet, nValueRet);
+        const int64_t t1 = GetTimeMicros();
+        const CoinSelectStats after = GetCoinSelectStats();
+        if (!ok || nValueRet < target) throw std::runtime_error("bench: the coin selection failed");
+        if (after.gpu_selections - before.gpu_selections != (arm == 2 ? 1u : 0u) ||
+            after.cpu_selections - before.cpu_selections != (arm == 1 ? 1u : 0u) || after.gpu_failures != before.gpu_failures)
+            throw std::runtime_error("bench: the coin selection did not take its arm's path");
+        if (iters >= 6) { // each arm's first runs grow buffers
+            ms[arm].push_back((t1 - t0) / 1000.0);
+            worst[arm] = std::max(worst[arm], nValueRet - target);
+        }
+        iters++;
+    }
+    SetCoinSelectTwinOnly(false);
+    SetGpuCoinSelectThreshold(keepThreshold);
+    for (int arm = 0; arm < 3; arm++) {
+        std::vector<double>& v = ms[arm];
+        std::sort(v.begin(), v.end());
+        printf("# coinselect coins=%zu %s: runs %zu, median %.3f ms (min %.3f, max %.3f), largest excess over the target %.8f\n",
+               ncoins, armName[arm], v.size(), v[v.size() / 2], v.front(), v.back(), worst[arm] / 100000000.0);
+    }
+}
+static bench::Reg reg_CoinSelect1k("CoinSelect_Coins1k", [](State& st) { CoinSelectBench(st, 1000); });
+static bench::Reg reg_CoinSelect10k("CoinSelect_Coins10k", [](State& st) { CoinSelectBench(st, 10000); });
+static bench::Reg reg_CoinSelect100k("CoinSelect_Coins100k", [](State& st) { CoinSelectBench(st, 100000); });
 
 int main(int argc, char* argv[]) {
     gArgs.ParseParameters(argc, argv);

@@ -10,6 +10,7 @@
 #include "script/sign.h"
 #include "util/strencodings.h"
 #include "util/util.h"
+#include "wallet/coinselect.h"
 #include "wallet/walletscan.h"
 
 #include <algorithm>
@@ -1393,9 +1394,17 @@ bool CWallet::SelectCoinsMinConf(Amount nTargetValue, int nConfMine, int nConfTh
     std::sort(vValue.begin(), vValue.end(), [](const ValuedCoin& a, const ValuedCoin& b) { return a.first > b.first; });
     std::vector<char> vfBest;
     Amount nBest;
-    ApproximateBestSubset(vValue, nTotalLower, nTargetValue, vfBest, nBest);
-    if (nBest != nTargetValue && nTotalLower >= nTargetValue + MIN_CHANGE)
-        ApproximateBestSubset(vValue, nTotalLower, nTargetValue + MIN_CHANGE, vfBest, nBest);
+    bool allowGpu = false;
+    if (GpuCoinSelectWanted(vValue.size(), &allowGpu) && vValue.back().first > 0 && nTargetValue > 0) {
+        // a long list: both searches as one batch of side-by-side trials (wallet/coinselect.h)
+        std::vector<Amount> values(vValue.size());
+        for (size_t i = 0; i < vValue.size(); i++) values[i] = vValue[i].first;
+        ApproximateBestSubsetBatched(values, nTotalLower, nTargetValue, MIN_CHANGE, allowGpu, vfBest, nBest);
+    } else {
+        ApproximateBestSubset(vValue, nTotalLower, nTargetValue, vfBest, nBest);
+        if (nBest != nTargetValue && nTotalLower >= nTargetValue + MIN_CHANGE)
+            ApproximateBestSubset(vValue, nTotalLower, nTargetValue + MIN_CHANGE, vfBest, nBest);
+    }
     if (coinLowestLarger.second.first &&
         ((nBest != nTargetValue && nBest < nTargetValue + MIN_CHANGE) || coinLowestLarger.first <= nBest)) {
         setCoinsRet.insert(coinLowestLarger.second);

@@ -27,6 +27,8 @@
 #   ibd TAG [BLOCKS] [SECS]  IBD runs, plus interleaved A/Bs of -connectlookahead and -connectinplace:
 #                            per-run ms/block, median/min/max per configuration, phase split
 #   relay TAG            BIP152 short-id kernel: GPU tests and the CPU vs GPU micro-bench; the wallet scan bench cases
+#   coinselect TAG       coin selection: its GPU tests, the three-arm SelectCoinsMinConf bench at 1k/10k/100k coins, a
+#                        kernel trace of the same
 #   lanes TAG            verify-service tests, then a 199k-signature and a 2000-header batch over
 #                        lanes [0], [0,0], [0,0,0,0] (sharding overhead) and the host-built-state
 #                        header path, with a kernel trace of the 2000-header runs
@@ -186,6 +188,18 @@ relay)
   # the wallet over a 21k-transaction block: the loop against the batched scan (profiles/wallet_scan.md)
   timeout -k 10 300 ./bin/bench_bcp -filter='WalletScan_.*' -time=4 > "$O/wallet_scan.log" 2>&1
   grep '^# walletscan' "$O/wallet_scan.log" ;;
+coinselect)
+  timeout -k 10 300 python -u -m pytest tests/test_coin_select_gpu.py tests/test_functional_gpu_coin_select.py -m gpu -x -v \
+    --timeout 120 --timeout-method thread > "$O/pytest.log" 2>&1 || { tail -n 30 "$O/pytest.log"; exit 1; }
+  tail -n 2 "$O/pytest.log"
+  # SelectCoinsMinConf at 1k, 10k and 100k coins: the serial loop, the host twin, the device (profiles/coin_select.md)
+  timeout -k 10 500 ./bin/bench_bcp -filter='CoinSelect_.*' -time=1 > "$O/coin_select.log" 2>&1
+  grep '^# coinselect' "$O/coin_select.log"
+  # the kernels' own time, in a run of its own
+  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o cs -- "$R/bin/bench_bcp" \
+    -filter='CoinSelect_Coins(1k|10k)' -time=1 > "$O/prof.log" 2>&1)
+  (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof100k" -o cs -- "$R/bin/bench_bcp" \
+    -filter='CoinSelect_Coins100k' -time=1 > "$O/prof100k.log" 2>&1) ;;
 lanes)
   timeout -k 10 400 python -u -m pytest tests/test_gpu_verify_service.py -m gpu -x -v --timeout 300 --timeout-method thread \
     > "$O/pytest.log" 2>&1 || { tail -n 30 "$O/pytest.log"; exit 1; }
